@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the SMGP ELBO hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -21,6 +21,17 @@ north_star layout (experts sharded, one all_to_all).  Timing: W warmup steps,
 then the K timed steps as `--repeats` blocks (default 5 x 50), each bracketed by
 barrier + synchronize, max over ranks; `value` = the median block rate in
 units of whole-config evaluations (weak: world_size evaluations per step).
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`,
+`ms_per_step` and the description of the workload.  `--full` adds, after the timed
+steps, everything that takes runs of its own: the per-stage event brackets with the
+per-kernel and roofline figures (`kernels`, `roofline`, `kuf_hbm`), the training-step
+leg (`train`), the other K5 image formats and plane counts (`k5_modes`) and the CPU
+baseline (`cpu_baseline`); without it those fields are empty.  `--dump-outputs DIR`
+writes what the last timed step computed as DIR/<name>.npy (float32): `elbo`, and
+`mu_f`, `var_f`, `mu_a`, `var_a`, the conditionals it was reduced from.  Inputs,
+variational state and the Philox key sequence are seeded, so equal arguments give
+equal inputs in every run.
 
 Rank 0 prints ONE JSON line (see README/DESIGN for the fields).
 """
@@ -72,16 +83,28 @@ def parse():
     ap.add_argument("--cross", default=None, choices=("f16", "f8"),
                     help="split-f16 K5: cross terms a_hi b_lo + a_lo b_hi on f16 (3 f16 products) or on one "
                          "e4m3 MFMA per two k-steps (f16x8); default: modulatedgps_amd.config")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-modes", action="store_true", help="skip the reduced-plane K5 side measurements")
-    ap.add_argument("--no-train", action="store_true", help="skip the training-step (ELBO + gradient + Adam) leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements: per-stage event brackets and "
+                         "the roofline figures, the training-step leg, the other K5 formats / planes, the CPU "
+                         "baseline (a plain run leaves these fields empty)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the ELBO and the four conditional arrays "
+                         "it was reduced from) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-modes", action="store_true",
+                    help="--full: skip the reduced-plane K5 side measurements")
+    ap.add_argument("--no-train", action="store_true",
+                    help="--full: skip the training-step (ELBO + gradient + Adam) leg")
     ap.add_argument("--layout", default="data", choices=("data", "expert"),
                     help="multi-GPU layout: 'data' shards N (weak scaling, the default); 'expert' shards the "
                          "K experts over the ranks on a fixed N (the north_star layout, strong scaling)")
     ap.add_argument("--cpu-sample", type=int, nargs=2, default=(8192, 65536),
                     help="two N sizes of the CPU oracle sample (linear fit in N; the full N "
                          "is timed directly when it is one of them)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def timed_blocks(step, steps, repeats, barrier, world, device, timing=None):
@@ -185,6 +208,27 @@ def stage_stats(timing):
         ts = [a.elapsed_time(b) for a, b in pairs]
         out[name] = (float(np.mean(ts)), len(ts))
     return out
+
+
+def dump_outputs(path, elbo, model, N, expert):
+    """--dump-outputs: the last timed step's results as <path>/<name>.npy (float32).
+    elbo [1]: the value _build_likelihood returned.  mu_f, var_f, mu_a, var_a [K, N]:
+    both layers' conditionals of that step, the arrays the ELBO is reduced from (they
+    do not depend on the Philox noise; the model's own buffers, read before anything
+    else runs on them).  At c3 4 x 2 MB; a seeded column sample above 64 MB in all."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"elbo": elbo.detach().float().cpu().numpy()}
+    if not expert:   # the expert layout holds its shard's conditionals inside distributed.py
+        b = model._buffers(N)
+        cols = None
+        if 4 * model.K * N * 4 > 60e6:
+            cols = torch.from_numpy(np.sort(np.random.default_rng(5).choice(
+                N, int(60e6) // (16 * model.K), replace=False))).to(model.device)
+        for name in ("mu_f", "var_f", "mu_a", "var_a"):
+            a = b[name] if cols is None else b[name].index_select(1, cols)
+            arrays[name] = a.float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def cpu_baseline(cfg, sizes):
@@ -406,11 +450,14 @@ def main():
     blocks, elbo = timed_blocks(elbo_step, args.steps, args.repeats, barrier, world, device)
     elbo_val = float(elbo.item())
     info = model.last_info.cpu().tolist() if model.last_info is not None else None
-    # per-stage event brackets in a separate, untimed block: an event record between
-    # two kernels costs ~10 us of idle GPU, so the timed steps carry none
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, elbo, model, N, expert)
+    # --full: per-stage event brackets in a separate, untimed block: an event record
+    # between two kernels costs ~10 us of idle GPU, so the timed steps carry none
     timing = {}
-    stage_steps = min(20, args.steps)
-    timed_blocks(elbo_step, stage_steps, 1, barrier, world, device, timing)
+    if args.full:
+        stage_steps = min(20, args.steps)
+        timed_blocks(elbo_step, stage_steps, 1, barrier, world, device, timing)
     st = stage_stats(timing)
 
     # algorithmic work per launch
@@ -425,7 +472,7 @@ def main():
     chol_flops = 2 * (2.0 * M ** 3 / 3.0)        # potrf + trtri, both layers (one batched sweep)
     kernels = {}
     from modulatedgps_amd.config import step_schedule
-    if "rbf_kuf" in st or (x6 and step_schedule() == "k1_in_k3"):
+    if args.full and ("rbf_kuf" in st or (x6 and step_schedule() == "k1_in_k3")):
         ms = probe_kuf(model, X, x6, fmt="f16" if f16 else "x6")
         kernels["rbf_kuf"] = {"bound": "hbm", "avg_us": ms * 1e3, "bytes": kuf_bytes,
                               "achieved": kuf_bytes / (ms * 1e-3) / 1e9, "unit": "GB/s",
@@ -483,12 +530,14 @@ def main():
     # N points per step; strong / expert = one evaluation of the config's N per step
     units = 1 if (expert or strong) else world
     value, ms_per_step, block_rates = median_rate(blocks, units)
-    train = None if (args.no_train or expert) else train_leg(model, X, Y, kw, args, barrier, world, device, units)
+    train = None
+    if args.full and not (args.no_train or expert):
+        train = train_leg(model, X, Y, kw, args, barrier, world, device, units)
     modes = None
-    if world == 1 and x6 and args.planes == 3 and not args.no_modes:
+    if args.full and world == 1 and x6 and args.planes == 3 and not args.no_modes:
         modes = k5_modes_leg(elbo_step, args, fmt)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sizes = tuple(args.cpu_sample)
         if cfg[0] < max(sizes):   # c4r / c2: sample at and below the config's own N
             sizes = (cfg[0] // 4, cfg[0])
@@ -502,7 +551,7 @@ def main():
             "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
             # N = 1: both layouts are the same run; it is reported under the chosen series
             "scaling": "strong" if (expert or strong or (world == 1 and args.scaling == "strong")) else "weak",
-            "vs_baseline": None,
+            "vs_baseline": None, "full": bool(args.full),
             "repeats": len(blocks), "steps_per_repeat": [n for n, _ in blocks], "block_rates": block_rates,
             "dtype": (("f32 (split-f16 + e4m3 cross terms)" if f16x8 else "f32 (split-f16, 22-bit operands)")
                       if f16 else {3: "f32 (split-bf16 x6, f32-exact operands)", 2: "f32/bf16x3 mixed",

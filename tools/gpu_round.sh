@@ -10,9 +10,12 @@ if [ -z "${SKIP_TESTS:-}" ]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread > gpurun_out/pytest_gpu.log 2>&1
   tail -2 gpurun_out/pytest_gpu.log
 fi
-timeout -k 10 600 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err
-tail -c 300 gpurun_out/bench.json
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o bench -- python3 bench.py > gpurun_out/bench_prof.json 2> gpurun_out/bench_prof.err
+# the bench line with every side measurement (bench.py --full), into $BENCH_OUT
+BENCH_OUT=${BENCH_OUT:-bench_out}
+mkdir -p $BENCH_OUT
+timeout -k 10 600 python bench.py --full > $BENCH_OUT/bench.json 2> $BENCH_OUT/bench.err
+tail -c 300 $BENCH_OUT/bench.json
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $BENCH_OUT/prof -o bench -- python3 bench.py --full > $BENCH_OUT/bench_prof.json 2> $BENCH_OUT/bench_prof.err
 timeout -k 10 300 python tools/bench_kernels.py > gpurun_out/bench_kernels.json 2> gpurun_out/bench_kernels.err
 ONLY=${ONLY:-} bash tools/pmc_pass.sh
 python tools/pmc_summary.py gpurun_out gpurun_out/pmc_traffic.json > /dev/null

@@ -3,7 +3,8 @@ under `rocprofv3 --kernel-trace`): start / end / duration (us, relative to the
 step's chol_prep) and queue of every dispatch between two chol_prep launches;
 the K3 step launches are summarised on one line (with --steps: one line per launch,
 its duration and the gap to the previous launch).
-Usage: python tools/timeline.py gpurun_out/prof/bench_kernel_trace.csv [step index] [--steps]"""
+Usage: python tools/timeline.py bench_out/prof/bench_kernel_trace.csv [step index] [--steps]
+(the trace tools/gpu_round.sh takes of `bench.py --full`)"""
 import csv
 import sys
 
