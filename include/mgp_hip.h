@@ -344,6 +344,34 @@ int mgp_expert_conditional_f16c(const void* Afr, size_t afr_bytes, const void* L
                                 void* workspace, size_t workspace_bytes, void* Cfr, size_t cfr_bytes,
                                 const float* colmax, mgp_stream_t stream);
 
+/* ---------------------------------------------------------------- full covariance
+ * The whitened conditional with full_cov=True: GPflow base_conditional(..., full_cov=True,
+ * white=True) with Knn = kernel(Xnew, full_cov=True), as the reference's posterior plugin
+ * passes full_cov through (models.py:133-143; SVGP.predict_f(Xnew, full_cov=True) and
+ * predict_f_samples).  For every expert k and every pair i, j < N:
+ *   cov[k][i][j] = var exp(-0.5 sum_d ((X[i,d] - X[j,d]) / ls[d])^2)      (Knn, no jitter)
+ *                  - sum_m A[m,i] A[m,j] + sum_m C_k[m,i] C_k[m,j],   C_k = L_k^T A,
+ * with A = L^-1 K(Z, X) [M][lda] in float32 (what K4 writes into its A buffer:
+ * mgp_trsm_stats, mgp_trsm_stats_x6, mgp_trsm_stats_f16) and L_k = band_part(q_sqrt[k],
+ * -1, 0) (q_sqrt [K][M][ldqs] at element stride strideq).  X [N][ldx]; n_ls = 1 or D;
+ * D <= 32 and K <= 32 (MGP_ERR_UNSUPPORTED beyond).  cov: [K][N][ldc] at element stride
+ * stridec; each cov[k] is bitwise symmetric (the upper triangle is a copy of the lower),
+ * its diagonal is the marginal fvar of mgp_expert_conditional, and columns N .. ldc - 1
+ * are not written.  Exact-f32 MFMA products, f32 accumulation; A^T A is formed once for
+ * all K experts and only the lower-triangle tiles are computed.  The workspace holds
+ * C_k: mgp_full_cov_workspace_bytes(M, N, K) >= K M N floats.  lda, ldqs, ldc (and
+ * strideq, stridec when K > 1) must be multiples of 4 and A, q_sqrt, cov, workspace
+ * 16-B aligned (MGP_ERR_ALIGN).  N, M or K <= 0: MGP_OK, nothing is done.
+ * -1 X, -2 ldx < D, -4 D < 1, -5 variance, -6 lengthscales, -7 n_ls, -8 A, -9 lda < N,
+ * -10 q_sqrt, -11 ldqs < M, -12 strideq < ldqs M (K > 1), -15 cov, -16 ldc < N,
+ * -17 stridec < ldc N (K > 1); all checked before any pointer is read or HIP call made. */
+size_t mgp_full_cov_workspace_bytes(int64_t M, int64_t N, int32_t K);
+int mgp_full_cov_conditional(const float* X, int64_t ldx, int64_t N, int32_t D, const float* variance,
+                             const float* lengthscales, int32_t n_ls, const float* A, int64_t lda,
+                             const float* q_sqrt, int64_t ldqs, int64_t strideq, int64_t M, int32_t K,
+                             float* cov, int64_t ldc, int64_t stridec, void* workspace,
+                             size_t workspace_bytes, mgp_stream_t stream);
+
 /* ---------------------------------------------------------------- backward of K1-K5
  * Gram products over the data dimension (float32 MFMA, deterministic split-K):
  *   out[i][j] = alpha * sum_n X[i][n] Y[j][n]   (tri != 0: j <= i only, zeros above)
@@ -718,7 +746,8 @@ enum {
   MGP_OP_ELBO_TERMS_BACKWARD = 8,
   MGP_OP_CONDITIONAL_BACKWARD = 9,
   MGP_OP_CHOL_BACKWARD = 10,
-  MGP_OP_RBF_BACKWARD = 11
+  MGP_OP_RBF_BACKWARD = 11,
+  MGP_OP_FULL_COV_CONDITIONAL = 12
 };
 size_t mgp_workspace_bytes(int32_t op, int64_t M, int64_t N, int32_t K);
 /* Kuu = K(Z, Z) + jitter I in float32 (covariances.Kuu, models.py:135); same as

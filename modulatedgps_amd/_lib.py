@@ -68,6 +68,11 @@ SIGNATURES = {
     "mgp_expert_conditional_f32": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr,
                                                   c_i64, c_i64, c_i32, c_ptr, c_ptr, c_i64, c_ptr, c_size,
                                                   c_ptr]),
+    # full_cov=True conditional (csrc/fullcov.hip)
+    "mgp_full_cov_workspace_bytes": (c_size, [c_i64, c_i64, c_i32]),
+    "mgp_full_cov_conditional": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_i32, c_ptr, c_i64,
+                                                c_ptr, c_i64, c_i64, c_i64, c_i32, c_ptr, c_i64, c_i64, c_ptr,
+                                                c_size, c_ptr]),
     # the SURVEY §8(b) front (csrc/front.hip)
     "mgp_workspace_bytes": (c_size, [c_i32, c_i64, c_i64, c_i32]),
     "mgp_rbf_kuu_jitter": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_i32, ctypes.c_float,

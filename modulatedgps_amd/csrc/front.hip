@@ -121,6 +121,8 @@ extern "C" size_t mgp_workspace_bytes(int32_t op, int64_t M, int64_t N, int32_t 
       return mgp_chol_backward_workspace_bytes(M);
     case MGP_OP_RBF_BACKWARD:
       return mgp_rbf_backward_workspace_bytes(N, M, K);   // K carries D here
+    case MGP_OP_FULL_COV_CONDITIONAL:
+      return mgp_full_cov_workspace_bytes(M, N, K);
     default:
       return 0;
   }

@@ -147,6 +147,7 @@ class SVGPModified:
             Z = Z[:, None]
         self.Z = Z.contiguous()
         self._last_info = None
+        self.seed, self._draws = 0, 0   # Philox key stream of predict_f_samples
         M = self.Z.shape[0]
         self.num_latent_gps = int(num_latent_gps)
         K = self.num_latent_gps
@@ -341,9 +342,112 @@ class SVGPModified:
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False, tiled=None):
         """GPflow SVGP.predict_f(Xnew): posterior(NOCACHE).fused_predict_f, i.e. the
         Modified posterior's _conditional_fused (models.py:129-144).
-        Xnew [..., N, D] -> mean, var [..., N, K].  tiled: see _marginals_kn."""
+        Xnew [..., N, D] -> mean, var [..., N, K]; full_cov=True: mean [..., N, K] and
+        cov [..., K, N, N] (see _full_cov).  tiled: see _marginals_kn."""
         return self.posterior(PrecomputeCacheType.NOCACHE).fused_predict_f(Xnew, full_cov, full_output_cov,
                                                                           tiled=tiled)
+
+    # ------------------------------------------------------------------ full covariance
+    def next_seed(self):
+        """Fresh Philox key per sampling call of the layer (as SMGP.next_seed)."""
+        self._draws += 1
+        return _splitmix64(self.seed * 0x100000001B3 + self._draws)
+
+    def conditional_full_cov_kn(self, X):
+        """X [N, D] -> fmean [K, N] (conditional_kn's) and cov [K, N, N]: the chain
+        K1 -> K3 -> K4 -> K5 as conditional_kn runs it, with K4 also writing the f32 A,
+        then mgp_full_cov_conditional on that A (base_conditional, full_cov=True)."""
+        X = self.kernel._x(X)
+        A = ops.padded(self.num_inducing, X.shape[0], self.device)
+        fm, _ = self.conditional_kn(X, bufs={"A" if conditional_mode() == "f32" else "A32": A})
+        cov = ops.full_cov_conditional(X, A, self.q_sqrt, self.kernel.variance, self.kernel.lengthscales)
+        return fm, cov
+
+    def _full_cov(self, Xnew, tiled=None):
+        """Xnew [..., N, D] -> mean [..., N, K], cov [..., K, N, N] (GPflow's [..., P, N, N]).
+        Leading dimensions are batch: each leading index has its own N x N blocks.  Tiled
+        copies of one input (recognised as in _marginals_kn, or tiled=True) are computed
+        once and returned as expand() views; distinct leading slices are computed in turn."""
+        if not isinstance(Xnew, torch.Tensor):
+            Xnew = torch.as_tensor(np.asarray(Xnew))
+        if Xnew.dim() <= 2:
+            fm, cov = self.conditional_full_cov_kn(Xnew)
+            return fm.t(), cov
+        lead, N = Xnew.shape[:-2], Xnew.shape[-2]
+        K = self.num_latent_gps
+        if tiled is None:
+            if Xnew.device.type == "cpu":
+                X2 = Xnew.reshape(-1, *Xnew.shape[-2:])
+                tiled = X2.shape[0] > 1 and bool(torch.equal(X2, X2[:1].expand_as(X2)))
+            else:
+                tiled = all(st == 0 for st, n in zip(Xnew.stride()[:len(lead)], lead) if n > 1)
+        if tiled:
+            fm, cov = self.conditional_full_cov_kn(Xnew[(0,) * len(lead)])
+            return fm.t().expand(*lead, N, K), cov.expand(*lead, K, N, N)
+        outs = [self.conditional_full_cov_kn(x) for x in Xnew.reshape(-1, *Xnew.shape[-2:])]
+        mean = torch.stack([fm.t() for fm, _ in outs]).reshape(*lead, N, K)
+        return mean, torch.stack([cov for _, cov in outs]).reshape(*lead, K, N, N)
+
+    def _chol_full_cov(self, cov, jitter):
+        """chol(cov[..., k] + jitter I) [..., K, N, N] (lower, zeros above) by the float64
+        K3 (mgp_potrf_trtri, at most 8 matrices per call); MGPLinAlgError on a non-positive
+        pivot.  Expanded (tiled) leading dimensions are factorised once."""
+        lead = cov.shape[:-3]
+        if len(lead) and all(st == 0 for st, n in zip(cov.stride(), lead) if n > 1):
+            return self._chol_full_cov(cov[(0,) * len(lead)], jitter).expand(cov.shape)
+        N = cov.shape[-1]
+        mats = cov.reshape(-1, N, N)
+        B = mats.shape[0]
+        Aj = ops.padded(N, N, self.device, batch=B)
+        Aj.copy_(mats)
+        Aj.diagonal(dim1=-2, dim2=-1).add_(jitter)
+        L = ops.padded(N, N, self.device, batch=B)
+        info = torch.empty(B, dtype=torch.int32, device=self.device)
+        for b0 in range(0, B, 8):
+            b1 = min(b0 + 8, B)
+            ops.potrf_trtri(Aj[b0:b1], L=L[b0:b1], info=info[b0:b1])
+        ops.check_info(info)
+        return L.unflatten(0, tuple(cov.shape[:-2]))
+
+    def predict_f_samples(self, Xnew, num_samples=None, full_cov=True, full_output_cov=False, noise=None,
+                          seed=None, jitter=None, tiled=None):
+        """GPflow GPModel.predict_f_samples (sample_mvn): joint samples of the K latent
+        functions at Xnew [..., N, D] -> [..., S, N, K] ([..., N, K] for num_samples=None):
+            samples[..., s, :, k] = mean[..., :, k] + chol(cov[..., k] + jitter I) noise[..., s, :, k]
+        with predict_f(Xnew, full_cov=True)'s mean and cov; full_cov=False draws from the
+        marginals, mean + sqrt(var + jitter) noise.  noise: explicit standard normals of the
+        samples' shape; else Philox normals (ops.philox_normal2) keyed by `seed`, or by a
+        fresh key of the layer per call.  jitter defaults to default_jitter().
+
+        Float32 limit: a float32 covariance of densely spaced points is positive definite
+        only down to about sqrt(N) * 6e-8 * variance, so the default jitter of 1e-6 holds
+        for N in the hundreds (minimum eigenvalues of -7e-8 .. -3.5e-7 at N = 100 .. 200) but
+        not for N in the thousands.  The default is not raised silently: a failed
+        factorisation raises MGPLinAlgError, and the caller passes a larger jitter."""
+        if full_output_cov:
+            raise NotImplementedError("full_output_cov predictions are not implemented")
+        jitter = default_jitter() if jitter is None else float(jitter)
+        mean, var = self.predict_f(Xnew, full_cov=full_cov, tiled=tiled)
+        lead, (N, K) = tuple(mean.shape[:-2]), mean.shape[-2:]
+        S = 1 if num_samples is None else int(num_samples)
+        shape = (*lead, S, N, K)
+        if noise is None:
+            B = int(np.prod(lead)) if lead else 1
+            key = self.next_seed() if seed is None else int(seed)
+            z = ops.philox_normal2(key, 0, N, K, B * S, self.device).reshape(shape)
+        else:
+            z = _to_dev(noise, self.device)
+            if num_samples is None and z.dim() == mean.dim():
+                z = z.unsqueeze(-3)
+            if tuple(z.shape) != shape:
+                raise ValueError(f"noise must have the samples' shape {shape}, got {tuple(z.shape)}")
+        if not full_cov:
+            samples = mean.unsqueeze(-3) + torch.sqrt(var.unsqueeze(-3) + jitter) * z
+        else:
+            L = self._chol_full_cov(var, jitter)                       # [..., K, N, N]
+            Lz = torch.matmul(L, z.permute(*range(len(lead)), -1, -2, -3))   # [..., K, N, S]
+            samples = mean.unsqueeze(-3) + Lz.permute(*range(len(lead)), -1, -2, -3)
+        return samples if num_samples is not None else samples.squeeze(-3)
 
 
 class PrecomputeCacheType:
@@ -376,9 +480,12 @@ class IndependentPosteriorSingleOutputModified:
         """(fmean, fvar) [..., N, K] of the whitened SVGP marginals (models.py:129-144).
         tiled (extension): True when the caller's [S, N, D] input holds S equal copies
         (computed once without a check), False to compute every row, None to detect
-        (SVGPModified._marginals_kn)."""
-        if full_cov or full_output_cov:
-            raise NotImplementedError("full_cov predictions are not used by the SMGP path")
+        (SVGPModified._marginals_kn).  full_cov=True: (fmean [..., N, K], cov [..., K, N, N])
+        of base_conditional(..., full_cov=True, white=True) (SVGPModified._full_cov)."""
+        if full_output_cov:
+            raise NotImplementedError("full_output_cov predictions are not implemented")
+        if full_cov:
+            return self._layer._full_cov(Xnew, tiled=tiled)
         fm, fv, S, N, stride, lead = self._layer._marginals_kn(Xnew, tiled=tiled)
         K = fm.shape[0]
         shape = (*lead, N, K)

@@ -201,7 +201,9 @@ def check_info(info):
     if bool((bad != 0).any()):
         raise _lib.MGPLinAlgError("mgp_potrf_trtri", int(bad.max()),
                                   "Cholesky decomposition was not successful: the input might "
-                                  "not be valid (non-positive pivot at column %s)" % bad.tolist())
+                                  "not be valid (non-positive pivot at column %s); a float32 "
+                                  "covariance of densely spaced points may need a larger jitter"
+                                  % bad.tolist())
 
 
 # --------------------------------------------------------------------------- K4 / K5
@@ -377,6 +379,37 @@ def expert_conditional(A, q_sqrt, stats, variance, fmean=None, fvar=None, worksp
               fmean.data_ptr(), fvar.data_ptr(), _ld(fmean), workspace.data_ptr(),
               workspace.numel(), _stream())
     return fmean, fvar
+
+
+def full_cov_workspace_bytes(M, N, K):
+    return max(int(_lib.load().mgp_full_cov_workspace_bytes(M, N, K)), 16)
+
+
+def full_cov_conditional(X, A, q_sqrt, variance, lengthscales, out=None, workspace=None):
+    """cov [K, N, N] of the whitened conditional with full_cov=True (base_conditional,
+    models.py:133-143): K(X, X) - A^T A + (L_k^T A)^T (L_k^T A) per expert, from the f32
+    A = L^-1 Kuf [M, N] that K4 writes (trsm_stats, or trsm_stats_x6 with an A buffer).
+    The result is a view of padded storage (leading dimension % 4 == 0), each cov[k]
+    bitwise symmetric; `out`, if given, must be such a view."""
+    _check(X, "X", 2), _check(A, "A", 2), _check(q_sqrt, "q_sqrt", 3)
+    _check(variance, "variance"), _check(lengthscales, "lengthscales")
+    N, D = X.shape
+    M = A.shape[0]
+    K = q_sqrt.shape[0]
+    if A.shape[1] != N or tuple(q_sqrt.shape[1:]) != (M, M):
+        raise ValueError(f"expected A [M, {N}] and q_sqrt [K, M, M], got {tuple(A.shape)} and {tuple(q_sqrt.shape)}")
+    dev = X.device
+    if out is None:
+        out = padded(N, N, dev, batch=K)
+    elif tuple(out.shape) != (K, N, N):
+        raise ValueError(f"out must be [{K}, {N}, {N}]")
+    nbytes = _lib.load().mgp_full_cov_workspace_bytes(M, N, K)
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = _ws(nbytes, dev)
+    _lib.call("mgp_full_cov_conditional", X.data_ptr(), _ld(X), N, D, variance.data_ptr(), lengthscales.data_ptr(),
+              lengthscales.numel(), A.data_ptr(), _ld(A), q_sqrt.data_ptr(), _ld(q_sqrt), q_sqrt.stride(0), M, K,
+              out.data_ptr(), _ld(out), out.stride(0), workspace.data_ptr(), workspace.numel(), _stream())
+    return out
 
 
 # ------------------------------------------------------------ K5, split-bf16 (x6)
