@@ -702,6 +702,43 @@ int mgp_e_log_p_y(const float* mu_f, const float* var_f, const float* mu_a, cons
                   float multiclass_eps, const float* W, int64_t N, int32_t K, int32_t S, float* out,
                   mgp_stream_t stream);
 
+/* ---------------------------------------------------------------- mixture predictive
+ * The predictive density of the mixture of experts, p(y | x) = sum_k w_k N(y | mu_f,k, s2_k)
+ * with s2_k = var_f,k + lik_var_k (likelihoods.py:31-32).  The reference has no
+ * counterpart (its demos scatter predict_samples points); the semantics are DESIGN's
+ * "Mixture predictive".  RelaxedOneHotCategorical(tau, logits) relaxes
+ * argmax_k(g_k + logit_k), whose class probabilities are softmax_k(logits) (Gumbel-max),
+ * so the Gumbel noise is integrated out and only the logits' Gaussian noise is sampled:
+ *   S >= 1: logits_s = mu_a + z_s sqrt(max(var_a + jitter, 0)),  w_k = mean_s softmax_k(logits_s)
+ *   S == 0: w_k = softmax_k(mu_a)     (mgp_predict_epilogue's assign; no noise, no jitter)
+ *   weights[n][k]  = w_k                                         [N][K] row-major
+ *   mix_mean[n]    = sum_k w_k mu_f,k
+ *   mix_var[n]     = sum_k w_k (s2_k + (mu_f,k - mix_mean)^2)
+ *   log_density[n] = logsumexp_{s,k}(log_softmax_k(logits_s) + log N(Y[n] | mu_f,k, s2_k)) - log S
+ *                    (S == 0: over k), max-subtracted, so it stays finite far in the tails
+ *   log_density_sum = sum_n log_density[n]   (one double; deterministic two-stage sum)
+ * Latents expert-major [K][ldf]; lik_var [K], Y [N] (device).  Noise: explicit noise_z
+ * [S][N][K], or (NULL) the Philox stream 0 of mgp_elbo_terms keyed by (seed, n + n_offset,
+ * s, k / 4) -- mgp_philox_noise(seed, n_offset, ...) writes the same z; no uniform is
+ * drawn.  Per-point outputs do not depend on how N is sharded.  Every output may be NULL;
+ * log_density / log_density_sum need Y (-7 otherwise).  -10: S < 0; -11: jitter < 0;
+ * -14: n_offset < 0; K > 32: MGP_ERR_UNSUPPORTED.  The workspace
+ * (mgp_mixture_predict_workspace_bytes(N, K)) is used, and checked, only when
+ * log_density_sum is not NULL.  N <= 0: MGP_OK, nothing done. */
+size_t mgp_mixture_predict_workspace_bytes(int64_t N, int32_t K);
+int mgp_mixture_predict(const float* mu_f, const float* var_f, const float* mu_a, const float* var_a,
+                        int64_t ldf, const float* lik_var, const float* Y, int64_t N, int32_t K, int32_t S,
+                        float jitter, const float* noise_z, uint64_t seed, int64_t n_offset, float* weights,
+                        float* mix_mean, float* mix_var, float* log_density, double* log_density_sum,
+                        void* workspace, size_t workspace_bytes, mgp_stream_t stream);
+/* density[n][g] = sum_k weights[n][k] N(y_grid[g] | mu_f,k[n], var_f,k[n] + lik_var_k):
+ * the mixture density on a grid of G targets shared by all points, from the weights
+ * [N][K] of mgp_mixture_predict.  density [N][ldd >= G] row-major.  N <= 0 or G == 0:
+ * MGP_OK, nothing done; K > 32: MGP_ERR_UNSUPPORTED. */
+int mgp_mixture_density_grid(const float* mu_f, const float* var_f, int64_t ldf, const float* lik_var,
+                             const float* weights, int64_t N, int32_t K, const float* y_grid, int32_t G,
+                             float* density, int64_t ldd, mgp_stream_t stream);
+
 /* ---------------------------------------------------------------- optimizer
  * KL gradient folded into the ELBO gradient: g_q_mu -= q_mu / num_data,
  * g_q_sqrt[k] -= tril(L_k - diag(1 / L_k[m,m])) / num_data (models.py:79). */
@@ -747,7 +784,8 @@ enum {
   MGP_OP_CONDITIONAL_BACKWARD = 9,
   MGP_OP_CHOL_BACKWARD = 10,
   MGP_OP_RBF_BACKWARD = 11,
-  MGP_OP_FULL_COV_CONDITIONAL = 12
+  MGP_OP_FULL_COV_CONDITIONAL = 12,
+  MGP_OP_MIXTURE_PREDICT = 13
 };
 size_t mgp_workspace_bytes(int32_t op, int64_t M, int64_t N, int32_t K);
 /* Kuu = K(Z, Z) + jitter I in float32 (covariances.Kuu, models.py:135); same as

@@ -224,6 +224,13 @@ SIGNATURES = {
                                                  c_ptr, c_ptr]),
     "mgp_e_log_p_y": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, ctypes.c_float,
                                      c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr]),
+    # the mixture predictive (csrc/mixture.hip)
+    "mgp_mixture_predict_workspace_bytes": (c_size, [c_i64, c_i32]),
+    "mgp_mixture_predict": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_i32,
+                                           ctypes.c_float, c_ptr, c_u64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                           c_ptr, c_size, c_ptr]),
+    "mgp_mixture_density_grid": (ctypes.c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_i32,
+                                                c_ptr, c_i64, c_ptr]),
 }
 
 _lib = None

@@ -123,6 +123,8 @@ extern "C" size_t mgp_workspace_bytes(int32_t op, int64_t M, int64_t N, int32_t 
       return mgp_rbf_backward_workspace_bytes(N, M, K);   // K carries D here
     case MGP_OP_FULL_COV_CONDITIONAL:
       return mgp_full_cov_workspace_bytes(M, N, K);
+    case MGP_OP_MIXTURE_PREDICT:
+      return mgp_mixture_predict_workspace_bytes(N, K);
     default:
       return 0;
   }

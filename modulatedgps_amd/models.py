@@ -1237,6 +1237,113 @@ class SMGP(SGP):
                                      S, TAU, noise=noise, seed=seed or 0, multiclass_eps=mc)
         return sy[..., None], sf[..., None]
 
+    # ------------------------------------------------------------------ mixture predictive
+    # p(y* | x*) = sum_k w_k N(y* | mu_f,k, var_f,k + sigma_k^2) with w = mean_s softmax_k(mu_a +
+    # z_s sqrt(var_a + jitter)) -- the Gumbel noise of RelaxedOneHotCategorical integrated out
+    # (its argmax has class probabilities softmax(logits)); S = 0: the plug-in weights of
+    # predict_assign.  The reference has no counterpart (DESIGN "Mixture predictive").  Each
+    # method runs one conditionals(X) and one mgp_mixture_predict.  noise_z: explicit normals
+    # [S, N, K]; else Philox with `seed` (K6's z stream; a fresh key per call when None).
+    def _mixture(self, Xnew, S, want, Y=None, noise_z=None, seed=None, n_offset=0):
+        if self._mc_eps() is not None:
+            raise NotImplementedError(
+                "a MultiClass pred likelihood has no expert mixture: W multiplies one value per point, "
+                "and predict_y already returns the class probabilities")
+        S = int(S)
+        if S < 0:
+            raise ValueError("S must be >= 0")
+        X = self.pred_layer.kernel._x(Xnew)
+        Yd = None
+        if Y is not None:
+            Yd = _to_dev(Y, self.device).reshape(-1).contiguous()
+            if Yd.numel() != X.shape[0]:
+                raise ValueError("X and Y must have the same number of rows")
+        if noise_z is not None:
+            noise_z = _to_dev(noise_z, self.device)
+        elif S >= 1 and seed is None:
+            seed = self.next_seed()
+        mu_f, var_f, mu_a, var_a = self.conditionals(X)
+        lik_var = self.likelihood.likelihood.variance.reshape(-1)
+        out = ops.mixture_predict(mu_f, var_f, mu_a, var_a, lik_var, S, Y=Yd, noise_z=noise_z, seed=seed or 0,
+                                  n_offset=n_offset, want=want)
+        return out, (mu_f, var_f, lik_var)
+
+    def predict_mixture_weights_device(self, Xnew, S=0, noise_z=None, seed=None):
+        """predict_mixture_weights as a float32 device tensor [N, K]."""
+        return self._mixture(Xnew, S, ("weights",), noise_z=noise_z, seed=seed)[0]["weights"]
+
+    def predict_mixture_weights(self, Xnew, S=0, noise_z=None, seed=None):
+        """The mixture weights w [N, K] (HostArray, float64): S = 0 is predict_assign; S >= 1
+        averages the softmax over S draws of the assignment GP's logits, so its variance counts."""
+        w = self.predict_mixture_weights_device(Xnew, S, noise_z=noise_z, seed=seed)
+        self.check_linalg()
+        return _host(w)
+
+    def predict_mixture_mean_and_var_device(self, Xnew, S=0, noise_z=None, seed=None):
+        """predict_mixture_mean_and_var as float32 device tensors ([N, 1], [N, 1])."""
+        out, _ = self._mixture(Xnew, S, ("mix_mean", "mix_var"), noise_z=noise_z, seed=seed)
+        return out["mix_mean"][:, None], out["mix_var"][:, None]
+
+    def predict_mixture_mean_and_var(self, Xnew, S=0, noise_z=None, seed=None):
+        """Mean and variance of the mixture predictive, ([N, 1], [N, 1]) (HostArray, float64):
+        sum_k w mu_f and sum_k w (var_f + sigma_k^2 + (mu_f - mean)^2)."""
+        m, v = self.predict_mixture_mean_and_var_device(Xnew, S, noise_z=noise_z, seed=seed)
+        self.check_linalg()
+        return _host(m), _host(v)
+
+    def predict_log_density_device(self, Xnew, Ynew, S=0, noise_z=None, seed=None):
+        """predict_log_density as a float32 device tensor [N]."""
+        return self._mixture(Xnew, S, ("log_density",), Y=Ynew, noise_z=noise_z, seed=seed)[0]["log_density"]
+
+    def predict_log_density(self, Xnew, Ynew, S=0, noise_z=None, seed=None):
+        """log p(Ynew | Xnew) of the mixture predictive per point, [N] (HostArray, float64; GPflow's
+        predict_log_density shape), a max-subtracted log-sum-exp that stays finite in the tails."""
+        ld = self.predict_log_density_device(Xnew, Ynew, S, noise_z=noise_z, seed=seed)
+        self.check_linalg()
+        return _host(ld)
+
+    def predict_density_device(self, Xnew, y_grid, S=0, noise_z=None, seed=None):
+        """predict_density as a float32 device tensor [N, G]."""
+        g = _to_dev(y_grid, self.device)
+        if g.dim() != 1:
+            raise ValueError("y_grid must be 1-D")
+        out, (mu_f, var_f, lik_var) = self._mixture(Xnew, S, ("weights",), noise_z=noise_z, seed=seed)
+        return ops.mixture_density_grid(mu_f, var_f, lik_var, out["weights"], g.contiguous())
+
+    def predict_density(self, Xnew, y_grid, S=0, noise_z=None, seed=None):
+        """The mixture predictive density p(y_grid[g] | Xnew[n]), [N, G] (HostArray, float64), on a
+        1-D grid of targets shared by all points."""
+        d = self.predict_density_device(Xnew, y_grid, S, noise_z=noise_z, seed=seed)
+        self.check_linalg()
+        return _host(d)
+
+    def log_predictive_density_device(self, X, Y, S=0, noise_z=None, seed=None, n_offset=0, n_total=None,
+                                      process_group=None):
+        """log_predictive_density as a 0-d float64 device tensor (no host sync)."""
+        out, (mu_f, _, _) = self._mixture(X, S, ("log_density_sum",), Y=Y, noise_z=noise_z, seed=seed,
+                                          n_offset=n_offset)
+        total, N = out["log_density_sum"], mu_f.shape[1]
+        f64 = dict(dtype=torch.float64, device=self.device)
+        sc = torch.cat([total, torch.full((1,), float(N), **f64)])
+        if process_group is not None:
+            import torch.distributed as dist
+            dist.all_reduce(sc, op=dist.ReduceOp.SUM, group=process_group)
+        # a tensor divisor in every case (a Python one is multiplied by as its reciprocal),
+        # so that a one-rank group gives the plain call's bits
+        return sc[0] / (sc[1] if n_total is None else torch.full((), float(n_total), **f64))
+
+    def log_predictive_density(self, X, Y, S=0, noise_z=None, seed=None, n_offset=0, n_total=None,
+                               process_group=None):
+        """Mean over all points of log p(Y | X) (the held-out log-likelihood; its negative is
+        the NLPD), a Python float from the float64 sum of the per-point values.  n_offset /
+        n_total / process_group: sharding over N as in _build_likelihood (each rank passes its
+        shard; one all-reduce of [sum, count]; without a group the local sum is divided by
+        n_total, so the shards' values add up to the one-call value)."""
+        v = self.log_predictive_density_device(X, Y, S, noise_z=noise_z, seed=seed, n_offset=n_offset,
+                                               n_total=n_total, process_group=process_group)
+        self.check_linalg()
+        return float(v.cpu())
+
 
 class SMGPModified(SMGP):
     """SMGP with a second (assignment) Gaussian likelihood on the assign layer

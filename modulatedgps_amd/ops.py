@@ -1146,3 +1146,88 @@ def e_log_p_y(mu_f, var_f, Y, lik_var, W, S, N, stride_s=0, mu_a=None, var_a=Non
               Y.data_ptr(), None if multiclass_eps is not None else lik_var.data_ptr(), ptr(assign_lik_var),
               float(multiclass_eps or 0.0), W.data_ptr(), N, K, S, out.data_ptr(), _stream())
     return out
+
+
+# --------------------------------------------------------------------------- mixture predictive
+MIXTURE_OUTPUTS = ("weights", "mix_mean", "mix_var", "log_density", "log_density_sum")
+
+
+def mixture_predict(mu_f, var_f, mu_a, var_a, lik_var, S=0, Y=None, noise_z=None, seed=0, n_offset=0,
+                    jitter=None, want=None, workspace=None, out=None):
+    """The mixture predictive p(y | x) = sum_k w_k N(y | mu_f,k, var_f,k + lik_var_k)
+    (mgp_mixture_predict, csrc/mixture.hip) -> dict of the outputs named in `want`:
+    weights [N, K], mix_mean [N], mix_var [N], log_density [N] (float32) and
+    log_density_sum [1] (float64).  w = mean_s softmax_k(mu_a + z_s sqrt(var_a + jitter));
+    S = 0: the plug-in softmax_k(mu_a).  noise_z: explicit normals [S, N, K], else K6's
+    Philox z stream of (seed, n_offset).  want defaults to every output Y allows; out: a
+    dict of an earlier call at the same shapes, whose tensors are written again."""
+    jitter = default_jitter() if jitter is None else jitter
+    for t, n in ((mu_f, "mu_f"), (var_f, "var_f"), (mu_a, "mu_a"), (var_a, "var_a")):
+        _check(t, n, 2)
+    ldf = _ld(mu_f)
+    if not (_ld(var_f) == _ld(mu_a) == _ld(var_a) == ldf):
+        raise ValueError("conditional outputs must share a leading dimension")
+    K, N = mu_f.shape
+    dev = mu_f.device
+    _check(lik_var, "lik_var")
+    if want is None:
+        want = MIXTURE_OUTPUTS if Y is not None else MIXTURE_OUTPUTS[:3]
+    unknown = [w for w in want if w not in MIXTURE_OUTPUTS]
+    if unknown:
+        raise ValueError(f"unknown outputs {unknown}; choose from {MIXTURE_OUTPUTS}")
+    yp = None
+    if Y is not None:
+        Y = Y.reshape(-1)
+        _check(Y, "Y")
+        if Y.numel() != N or not Y.is_contiguous():
+            raise ValueError("Y must be contiguous with N elements")
+        yp = Y.data_ptr()
+    elif "log_density" in want or "log_density_sum" in want:
+        raise ValueError("log_density needs Y")
+    zp = None
+    if noise_z is not None:
+        _check(noise_z, "noise_z", 3)
+        if tuple(noise_z.shape) != (S, N, K):
+            raise ValueError("explicit noise must be [S, N, K]")
+        noise_z = noise_z.contiguous()
+        zp = noise_z.data_ptr()
+    have, out = out or {}, {}
+    for name in want:
+        shape, dtype = ((N, K) if name == "weights" else (1,) if name == "log_density_sum" else (N,),
+                        torch.float64 if name == "log_density_sum" else F32)
+        t = have.get(name)
+        if t is not None:
+            if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"out[{name!r}] must be a contiguous {dtype} tensor of shape {shape}")
+        elif name == "log_density_sum" and N == 0:
+            t = torch.zeros(shape, dtype=dtype, device=dev)   # the entry does nothing for N = 0
+        else:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        out[name] = t
+    wp = wb = None
+    if "log_density_sum" in out:
+        nbytes = _lib.load().mgp_mixture_predict_workspace_bytes(N, K)
+        if workspace is None or workspace.numel() < nbytes:
+            workspace = _ws(nbytes, dev)
+        wp, wb = workspace.data_ptr(), workspace.numel()
+    ptr = lambda name: out[name].data_ptr() if name in out else None
+    _lib.call("mgp_mixture_predict", mu_f.data_ptr(), var_f.data_ptr(), mu_a.data_ptr(), var_a.data_ptr(), ldf,
+              lik_var.data_ptr(), yp, N, K, int(S), float(jitter), zp, int(seed) & 0xFFFFFFFFFFFFFFFF,
+              int(n_offset), *[ptr(n) for n in MIXTURE_OUTPUTS], wp, wb or 0, _stream())
+    return out
+
+
+def mixture_density_grid(mu_f, var_f, lik_var, weights, y_grid):
+    """density [N, G] = sum_k weights[n, k] N(y_grid[g] | mu_f,k[n], var_f,k[n] + lik_var_k)
+    (mgp_mixture_density_grid), from mixture_predict's weights [N, K]."""
+    _latents_check(mu_f, var_f, "f")
+    K, N = mu_f.shape
+    _check(lik_var, "lik_var"), _check(weights, "weights", 2), _check(y_grid, "y_grid", 1)
+    if tuple(weights.shape) != (N, K):
+        raise ValueError("weights must be [N, K]")
+    weights, y_grid = weights.contiguous(), y_grid.contiguous()
+    G = y_grid.numel()
+    out = torch.empty(N, G, dtype=F32, device=mu_f.device)
+    _lib.call("mgp_mixture_density_grid", mu_f.data_ptr(), var_f.data_ptr(), _ld(mu_f), lik_var.data_ptr(),
+              weights.data_ptr(), N, K, y_grid.data_ptr(), G, out.data_ptr(), max(G, 1), _stream())
+    return out
