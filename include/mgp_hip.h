@@ -25,6 +25,22 @@
  *    the legacy default stream) and acts on the current device.
  *  - Return value: MGP_OK (0); < 0: the (1-based) index of the first invalid
  *    argument, negated; > 0: an MGP_ERR_* code or MGP_ERR_HIP_BASE + hipError_t.
+ *  - Size limits (MGP_ERR_UNSUPPORTED one past them, before anything is launched or
+ *    written; each entry's comment repeats its own):
+ *      input dimension D <= 32: mgp_rbf_kuf, mgp_rbf_kuu (mgp_rbf_kuu_jitter),
+ *        mgp_rbf_kuf_x6 / _f16, the Kuf side job of mgp_kuu_potrf_trtri_kuf,
+ *        mgp_rbf_backward / _batch, mgp_full_cov_conditional;
+ *      D unbounded: mgp_kuu_potrf_trtri / _ev / _ex (a generic Kuu build above D = 32);
+ *      experts K <= 16: K4 (mgp_trsm_stats, _x6, _x6_f16, _f16, _f16x8, _f16_batch) and the
+ *        conditional backward (mgp_conditional_backward_*, its _prep_f16c);
+ *      experts K <= 32: K6 and its backward (mgp_elbo_terms*), mgp_relaxed_onehot_sample,
+ *        mgp_e_log_p_y, mgp_predict_samples*, mgp_multiclass_predict,
+ *        mgp_full_cov_conditional, mgp_mixture_predict / _density_grid and the front's
+ *        mgp_expert_conditional;
+ *      K unbounded: K5 on given statistics (mgp_expert_conditional_f32 / _x6 / _planes /
+ *        _f16*), the image splits, mgp_gauss_kl_white, mgp_predict_epilogue,
+ *        mgp_assign_logits, mgp_philox_noise / _normal2.
+ *    So the one chain that runs K in 17 .. 32 end to end is the SURVEY 8(b) front.
  */
 #ifndef MGP_HIP_H
 #define MGP_HIP_H
@@ -42,7 +58,8 @@ enum {
   MGP_OK = 0,
   MGP_ERR_WORKSPACE = 1,   /* workspace pointer NULL or too small */
   MGP_ERR_ALIGN = 2,       /* leading dimension / pointer alignment */
-  MGP_ERR_UNSUPPORTED = 3, /* size outside the supported range (e.g. D > 64, K > 32) */
+  MGP_ERR_UNSUPPORTED = 3, /* size outside the supported range: D > 32, K > 16 (K4, conditional
+                              backward) or K > 32 -- see "Size limits" above */
   MGP_ERR_HIP_BASE = 1000
 };
 
@@ -55,14 +72,15 @@ const char* mgp_status_string(int status);
  *   Kuf[m, n] = var * exp(-0.5 * sum_d ((Z[m,d] - X[n,d]) / ls[d])^2)
  * Replaces Kmn = self.kernel.K(self.X_data.Z, Xnew) (models.py:139; GPflow
  * SquaredExponential.K -> square_distance + K_r2).  n_ls = 1 (isotropic) or D
- * (ARD).  X: [N, D] (ld ldx), Z: [M, D] (ld ldz), Kuf: [M, N] (ld ldk % 4 == 0). */
+ * (ARD).  X: [N, D] (ld ldx), Z: [M, D] (ld ldz), Kuf: [M, N] (ld ldk % 4 == 0).
+ * D <= 32 (D > 32: MGP_ERR_UNSUPPORTED). */
 int mgp_rbf_kuf(const float* X, int64_t ldx, const float* Z, int64_t ldz, int64_t N, int64_t M,
                 int32_t D, const float* variance, const float* lengthscales, int32_t n_ls,
                 float* Kuf, int64_t ldk, mgp_stream_t stream);
 
 /* Kuu[i, j] = K(Z, Z)[i, j] + jitter * (i == j).
  * Replaces covariances.Kuu(self.X_data, self.kernel, jitter=default_jitter())
- * (models.py:135).  Kuu: [M, M] (ld ldk % 4 == 0). */
+ * (models.py:135).  Kuu: [M, M] (ld ldk % 4 == 0).  D <= 32 (D > 32: MGP_ERR_UNSUPPORTED). */
 int mgp_rbf_kuu(const float* Z, int64_t ldz, int64_t M, int32_t D, const float* variance,
                 const float* lengthscales, int32_t n_ls, float jitter, float* Kuu, int64_t ldk,
                 mgp_stream_t stream);
@@ -87,7 +105,8 @@ int mgp_potrf_trtri(const float* A, int64_t lda, int64_t strideA, int64_t M, int
  * float64 from Z_b inside the factorisation (fuses K2 into K3; replaces
  * covariances.Kuu at models.py:135 for the ELBO path).  Z, variance,
  * lengthscales: HOST arrays of `batch` (<= 8) DEVICE pointers; n_ls: host
- * array (1 or D per entry).  Every Z_b is [M, D] with leading dimension ldz. */
+ * array (1 or D per entry).  Every Z_b is [M, D] with leading dimension ldz.
+ * Any D >= 1 (the build stages Z in LDS up to D = 32 and reads it from memory above). */
 int mgp_kuu_potrf_trtri(const float* const* Z, int64_t ldz, int64_t M, int32_t D,
                         const float* const* variance, const float* const* lengthscales,
                         const int32_t* n_ls, float jitter, int32_t batch, float* L,
@@ -123,7 +142,8 @@ int mgp_kuu_potrf_trtri_ex(const float* const* Z, int64_t ldz, int64_t M, int32_
  * pointers, each at least mgp_x6_cols_bytes(M, N) bytes (kfr_bytes), 16-B aligned.
  * With M <= 64 (no step launches) the images are written by mgp_rbf_kuf_* launches
  * on the stream after the Kuu build.  -19 .. -24: X, ldx, N, Kfr, kfr_bytes,
- * kfr_format. */
+ * kfr_format.  D <= 32, the image kernels' limit (D > 32: MGP_ERR_UNSUPPORTED, nothing
+ * is factorised). */
 int mgp_kuu_potrf_trtri_kuf(const float* const* Z, int64_t ldz, int64_t M, int32_t D,
                             const float* const* variance, const float* const* lengthscales,
                             const int32_t* n_ls, float jitter, int32_t batch, float* L,
@@ -140,7 +160,8 @@ int mgp_kuu_potrf_trtri_kuf(const float* const* Z, int64_t ldz, int64_t M, int32
  * Replaces A = tf.linalg.triangular_solve(Lm, Kmn), sum(square(A), -2) and
  * fmean = matmul(A, f, transpose_a=True) in GPflow base_conditional
  * (models.py:141-143).  q_mu: [M, K] (ld ldq).  stats: [T][K+1][lds] with
- * T = mgp_stats_tiles(M); lds % 4 == 0, lds >= N. */
+ * T = mgp_stats_tiles(M); lds % 4 == 0, lds >= N.  K <= 16 (K > 16: MGP_ERR_UNSUPPORTED),
+ * here and in every image variant of K4 below. */
 int mgp_stats_tiles(int64_t M);
 int mgp_trsm_stats(const float* LinvT, int64_t ldl, const float* Kuf, int64_t ldk, int64_t M,
                    int64_t N, const float* q_mu, int64_t ldq, int32_t K, float* A, int64_t lda,
@@ -155,7 +176,8 @@ int mgp_trsm_stats(const float* LinvT, int64_t ldl, const float* Kuf, int64_t ld
  * tail of GPflow base_conditional (models.py:141-143; Knn = var from
  * models.py:133).  q_sqrt: [K][M][ldqs] at element stride strideq.
  * fmean, fvar: [K][ldf] (expert-major; ldf >= N).  Workspace (per-row-tile
- * partial sums): mgp_expert_workspace_bytes(M, N, K).  (Exact-f32 MFMA products;
+ * partial sums): mgp_expert_workspace_bytes(M, N, K).  Any K >= 1, as every K5 entry
+ * on given statistics (the experts are a grid dimension).  (Exact-f32 MFMA products;
  * the default-format entry of this operation is mgp_expert_conditional, below.) */
 size_t mgp_expert_workspace_bytes(int64_t M, int64_t N, int32_t K);
 int mgp_expert_conditional_f32(const float* A, int64_t lda, const float* q_sqrt, int64_t ldqs,
@@ -187,14 +209,17 @@ int mgp_split_cols_x6(const float* A, int64_t lda, int64_t M, int64_t N, void* A
 int mgp_split_upper_x6(const float* LinvT, int64_t ldl, int64_t M, void* Tfr, size_t tfr_bytes,
                        mgp_stream_t stream);
 /* K1 writing the image of Kuf directly (same arguments as mgp_rbf_kuf; the
- * f32 Kuf is not materialised). */
+ * f32 Kuf is not materialised).  D <= 32 (D > 32: MGP_ERR_UNSUPPORTED), also for
+ * mgp_rbf_kuf_f16. */
 int mgp_rbf_kuf_x6(const float* X, int64_t ldx, const float* Z, int64_t ldz, int64_t N, int64_t M,
                    int32_t D, const float* variance, const float* lengthscales, int32_t n_ls,
                    void* Kfr, size_t kfr_bytes, mgp_stream_t stream);
 /* K4 on images: A = LinvT^T Kuf from Tfr (mgp_split_upper_x6) and Kfr
  * (mgp_rbf_kuf_x6 / mgp_split_cols_x6), writing A's image Afr (for
  * mgp_expert_conditional_x6) and the stats exactly as mgp_trsm_stats; also
- * the f32 A [M][lda] when A is not NULL (kept for the backward pass). */
+ * the f32 A [M][lda] when A is not NULL (kept for the backward pass).  K <= 16
+ * (K > 16: MGP_ERR_UNSUPPORTED), as mgp_trsm_stats and the split-f16 variants
+ * mgp_trsm_stats_x6_f16 / _f16 / _f16x8 / _f16_batch. */
 int mgp_trsm_stats_x6(const void* Tfr, size_t tfr_bytes, const void* Kfr, size_t kfr_bytes, int64_t M,
                       int64_t N, const float* q_mu, int64_t ldq, int32_t K, void* Afr, size_t afr_bytes,
                       float* stats, int64_t lds, float* A, int64_t lda, mgp_stream_t stream);
@@ -433,7 +458,9 @@ int mgp_gram_f16_rows(const void* ximg, size_t ximg_bytes, int64_t MI, const flo
  * S_k = L_k L_k^T (sum_k L_k (L_k^T A) diag(G_v,k) = sum_k (S_k A) diag(G_v,k))
  * and P_k = A diag(G_v,k) A^T (g_q_sqrt[k] = 2 tril(P_k L_k)).  Every product
  * that scales with N runs on the split-bf16 x6 path (f32 accuracy), g_q_mu on
- * the f32 MFMA.  Workspace: mgp_conditional_backward_workspace_bytes. */
+ * the f32 MFMA.  Workspace: mgp_conditional_backward_workspace_bytes.  K <= 16
+ * (K > 16: MGP_ERR_UNSUPPORTED) for every mgp_conditional_backward_* entry and for
+ * mgp_conditional_backward_prep_f16c. */
 size_t mgp_conditional_backward_workspace_bytes(int64_t M, int64_t N, int32_t K);
 int mgp_conditional_backward_x6(const void* Afr, size_t afr_bytes, const float* A, int64_t lda,
                                 const float* q_sqrt, int64_t ldqs,
@@ -518,7 +545,8 @@ int mgp_chol_backward_batch(int32_t batch, const float* const* L, int64_t ldl, c
  * gZ [M][ldgz] (float), g_var and g_ls[n_ls] (double, device).  symmetric = 1
  * for Kuu (X = Z, symmetric gK: Z enters both arguments).  accumulate = 1 adds
  * to the outputs (to combine the Kuf and Kuu contributions).
- * Workspace: mgp_rbf_backward_workspace_bytes(N, M, D). */
+ * Workspace: mgp_rbf_backward_workspace_bytes(N, M, D).  D <= 32 (D > 32:
+ * MGP_ERR_UNSUPPORTED), also for mgp_rbf_backward_batch. */
 size_t mgp_rbf_backward_workspace_bytes(int64_t N, int64_t M, int32_t D);
 int mgp_rbf_backward(const float* X, int64_t ldx, const float* Z, int64_t ldz, int64_t N, int64_t M,
                      int32_t D, const float* variance, const float* lengthscales, int32_t n_ls,
@@ -565,7 +593,8 @@ int mgp_gauss_kl_white(const float* q_mu, int64_t ldq, const float* q_sqrt, int6
  * mu_*, var_*: [K][ldf]; Y: [N]; lik_var: [K] (device).  Noise: explicit
  * noise_z / noise_u [S][N][K] when both non-NULL (parity mode), else in-kernel
  * Philox4x32-10 keyed by (seed, global n = n_offset + n, s, k).  data_sum: one
- * double (device).  Workspace: mgp_elbo_workspace_bytes(N). */
+ * double (device).  Workspace: mgp_elbo_workspace_bytes(N).  K <= 32 (K > 32:
+ * MGP_ERR_UNSUPPORTED), as mgp_elbo_terms_modified and every K6 entry below. */
 size_t mgp_elbo_workspace_bytes(int64_t N);
 int mgp_elbo_terms(const float* mu_f, const float* var_f, const float* mu_a, const float* var_a,
                    int64_t ldf, const float* Y, const float* lik_var, int64_t N, int32_t K,
@@ -592,7 +621,8 @@ int mgp_elbo_terms_modified(const float* mu_f, const float* var_f, const float* 
  *   g_lik_var[K], g_assign_lik_var[K] (double, device) = scale * d(sum_n DT_n)/d(sigma^2)
  * (scale = 1 / N_total gives the ELBO's batch-mean gradient).  Replaces the
  * GradientTape pass through models.py:55-67,73-76 and likelihoods.py:39-41.
- * Workspace: mgp_elbo_backward_workspace_bytes(N, K). */
+ * Workspace: mgp_elbo_backward_workspace_bytes(N, K).  K <= 32 (K > 32:
+ * MGP_ERR_UNSUPPORTED). */
 size_t mgp_elbo_backward_workspace_bytes(int64_t N, int32_t K);
 int mgp_elbo_terms_backward(const float* mu_f, const float* var_f, const float* mu_a,
                             const float* var_a, int64_t ldf, const float* Y, const float* lik_var,
@@ -612,7 +642,8 @@ int mgp_elbo_combine(const double* data_sum, const double* kl_f, const double* k
  * SMGP.predict_assign, models.py:85-89):
  *   y_mean[n][k] = fmean[k][n]; y_var[n][k] = fvar[k][n] + lik_var[k]
  *   assign[n][k] = softmax_k(amean[k][n])
- * Any output may be NULL.  Outputs are [N][K] row-major (the reference layout). */
+ * Any output may be NULL.  Outputs are [N][K] row-major (the reference layout).
+ * Any K >= 1. */
 int mgp_predict_epilogue(const float* fmean, const float* fvar, const float* amean, int64_t ldf,
                          const float* lik_var, int64_t N, int32_t K, float* y_mean, float* y_var,
                          float* assign, mgp_stream_t stream);
@@ -623,7 +654,8 @@ int mgp_predict_epilogue(const float* fmean, const float* fvar, const float* ame
  *   samples_f[s][n] = sum_k W (mu_f + z sqrt(var_f + jitter))
  * (jitter: default_jitter(), the reparameterize of utils.py:26-27)
  * Explicit noise (all three [S][N][K], parity mode) or Philox (streams 0/1 for
- * W, stream 2 for z).  Outputs [S][N]; either may be NULL. */
+ * W, stream 2 for z).  Outputs [S][N]; either may be NULL.  K <= 32 (K > 32:
+ * MGP_ERR_UNSUPPORTED). */
 int mgp_predict_samples(const float* mu_f, const float* var_f, const float* mu_a, const float* var_a,
                         int64_t ldf, const float* lik_var, int64_t N, int32_t K, int32_t S, float tau, float jitter,
                         const float* noise_zw, const float* noise_uw, const float* noise_zy,
@@ -632,7 +664,8 @@ int mgp_predict_samples(const float* mu_f, const float* var_f, const float* mu_a
 
 /* Raw noise stream (for tests and for SMGP.predict_samples): writes
  * z[s][n][k] (normals) and/or u[s][n][k] (uniforms in (0,1)) exactly as
- * mgp_elbo_terms draws them in Philox mode.  Either pointer may be NULL. */
+ * mgp_elbo_terms draws them in Philox mode.  Either pointer may be NULL.  Any K >= 1
+ * ((K + 3) / 4 counter blocks per (s, n)), also for mgp_philox_normal2. */
 int mgp_philox_noise(uint64_t seed, int64_t n_offset, int64_t N, int32_t K, int32_t S, float* z,
                      float* u, mgp_stream_t stream);
 /* ---------------------------------------------------------------- MultiClass likelihood
@@ -646,7 +679,8 @@ int mgp_philox_noise(uint64_t seed, int64_t n_offset, int64_t N, int32_t K, int3
  * lik_var replaced by epsilon (0 < eps < 1, K >= 2); assign_lik_var != NULL
  * selects SMGPModified (its assign layer keeps the Gaussian likelihood).  The
  * backward has no likelihood-variance gradient (MultiClass has no trainable
- * parameter; RobustMax.epsilon is trainable=False). */
+ * parameter; RobustMax.epsilon is trainable=False).  2 <= K <= 32 (K > 32:
+ * MGP_ERR_UNSUPPORTED) for the four MultiClass entries. */
 int mgp_elbo_terms_multiclass(const float* mu_f, const float* var_f, const float* mu_a, const float* var_a,
                               int64_t ldf, const float* Y, float epsilon, const float* assign_lik_var,
                               int64_t N, int32_t K, int32_t S, float tau, float jitter, const float* noise_z,
@@ -680,7 +714,9 @@ int mgp_philox_normal2(uint64_t seed, int64_t n_offset, int64_t N, int32_t K, in
  * (stride_s = 0: one S-invariant conditional for S tiled copies of X).  Noise:
  * explicit [S][N][K] arrays (nullable) or K6's own Philox streams (z: stream 0,
  * u: stream 1, keyed by (n + n_offset, s, k / 4)), so the three calls below with
- * one seed reproduce mgp_elbo_terms with that seed.
+ * one seed reproduce mgp_elbo_terms with that seed.  mgp_assign_logits takes any
+ * K >= 1; mgp_relaxed_onehot_sample and mgp_e_log_p_y K <= 32 (K > 32:
+ * MGP_ERR_UNSUPPORTED).
  *
  * SMGP.W_dist (models.py:55-60): assign_layer.predict_f -> reparameterize
  * (utils.py:26-27): logits[s][n][k] = mu_a + z sqrt(var_a + jitter). */

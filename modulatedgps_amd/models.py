@@ -213,6 +213,7 @@ class SVGPModified:
         LinvT: (L^-1)^T of this layer's Kuu if already factorised (the SMGP
         factorises both layers in one batched sweep).  images: (Kfr, Lfr) from
         operand_images (x6 mode), if already built."""
+        ops.check_conditional_experts(self.num_latent_gps)
         X = self.kernel._x(X)
         if LinvT is None:
             _, LinvT, info = self.factorise()
@@ -745,6 +746,7 @@ class SMGP(SGP):
         latency-bound K3 sweep, which occupies only a few CUs.  They start once
         K3 has built Kuu (its prep event): launched beside the build, K1's 4096
         workgroups starve it (101 us instead of ~20)."""
+        ops.check_conditional_experts(self.K)
         X = self.pred_layer.kernel._x(X)
         N = X.shape[0]
         b = self._buffers(N, train)

@@ -207,6 +207,17 @@ def check_info(info):
 
 
 # --------------------------------------------------------------------------- K4 / K5
+MAX_EXPERTS_K4 = 16   # mgp_trsm_stats* and the conditional backward (MGP_ERR_UNSUPPORTED beyond)
+
+
+def check_conditional_experts(K):
+    """The layer conditional and its backward go through K4, which stops at K <= 16 (K5, K6
+    and the SURVEY §8(b) front take K <= 32): refuse before anything is launched."""
+    if K > MAX_EXPERTS_K4:
+        raise ValueError(f"K = {K} experts: the conditional path (K4, mgp_trsm_stats*, and the conditional "
+                         f"backward) supports K <= {MAX_EXPERTS_K4}")
+
+
 def stats_tiles(M):
     return _lib.load().mgp_stats_tiles(M)
 

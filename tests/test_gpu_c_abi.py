@@ -43,7 +43,11 @@ def _write_problem(path, X, Y, p, z, u):
 
 
 @pytest.mark.parametrize("N,M,K,D,ls,S", [(2000, 64, 3, 2, 0.8, 5), (4099, 130, 4, 3, 1.0, 9),
-                                          (65536, 1024, 8, 8, 1.0, 25)])   # BASELINE config 3 in full
+                                          (65536, 1024, 8, 8, 1.0, 25),    # BASELINE config 3 in full
+                                          # K > 16: K4 (mgp_trsm_stats*) stops at 16 experts, so these run
+                                          # --front alone, the one chain that takes K <= 32 end to end
+                                          # (D = 17, 32 with lengthscale 0.9 sqrt(D): rbf_kernel<32>)
+                                          (300, 40, 17, 17, 3.71, 3), (300, 70, 32, 32, 5.09, 3)])
 def test_elbo_through_the_c_abi_alone(device, tmp_path, N, M, K, D, ls, S):
     if not os.path.exists(BIN):
         pytest.fail(f"{BIN} is missing: run __graft_entry__.build() (it builds the C-ABI host program)")
@@ -51,12 +55,34 @@ def test_elbo_through_the_c_abi_alone(device, tmp_path, N, M, K, D, ls, S):
     z, u = R.explicit_noise(S, N, K, seed=5)
     prob = tmp_path / "problem.bin"
     _write_problem(prob, X, Y, p, z, u)
+    ref = R.smgp_elbo(X, Y, p, z, u)
+    if K <= 16:
+        _check_f16_chain(device, prob, X, Y, p, z, u, ref)
+    else:   # the split-f16 chain refuses K > 16 at its K4
+        r = subprocess.run([BIN, str(prob)], capture_output=True, text=True, timeout=120)
+        assert r.returncode != 0 and "mgp_trsm_stats_f16" in r.stderr, r.stdout + r.stderr
+    # the SURVEY §8(b) front names alone (mgp_rbf_kuu_jitter -> mgp_potrf_lower -> mgp_rbf_kuf ->
+    # mgp_trsm_lln -> mgp_expert_conditional -> mgp_gauss_kl_white).  Its Kuu is float32 (the
+    # front's interface) where the fused chain builds it in float64; measured (round 6): rel
+    # 1.8e-5 at cond(Kuu) 1.1e7, 1.2e-6 at 7.6e6, 5.3e-8 at BASELINE config 3 (cond 4.8e2)
+    rf = subprocess.run([BIN, str(prob), "--front"], capture_output=True, text=True, timeout=120)
+    assert rf.returncode == 0, rf.stdout + rf.stderr
+    lf = dict(l.split(" ", 1) for l in rf.stdout.strip().splitlines())
+    assert lf["info"].split() == ["0", "0"]
+    elbo_front = float(lf["elbo"])
+    cond = max(np.linalg.cond(R.rbf_Kuu(L["Z"], L["variance"], L["lengthscales"])) for L in (p.pred, p.assign))
+    print(f"front {elbo_front:.9g} (rel {abs(elbo_front - ref) / abs(ref):.2e}, cond(Kuu) {cond:.2e})")
+    assert elbo_front == pytest.approx(ref, rel=1e-4)
+
+
+def _check_f16_chain(device, prob, X, Y, p, z, u, ref):
+    """The split-f16 chain (one call per layer, then the batch entries) against the oracle and
+    the Python host."""
     r = subprocess.run([BIN, str(prob)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = dict(l.split(" ", 1) for l in r.stdout.strip().splitlines())
     assert lines["info"].split() == ["0", "0"]
     elbo_c = float(lines["elbo"])
-    ref = R.smgp_elbo(X, Y, p, z, u)
     model = build_model(p, device, seed=7)
     from modulatedgps_amd import config
     old = config.expert_format()
@@ -73,15 +99,3 @@ def test_elbo_through_the_c_abi_alone(device, tmp_path, N, M, K, D, ls, S):
     rb = subprocess.run([BIN, str(prob), "--batched"], capture_output=True, text=True, timeout=120)
     assert rb.returncode == 0, rb.stderr
     assert rb.stdout == r.stdout
-    # the SURVEY §8(b) front names alone (mgp_rbf_kuu_jitter -> mgp_potrf_lower -> mgp_rbf_kuf ->
-    # mgp_trsm_lln -> mgp_expert_conditional -> mgp_gauss_kl_white).  Its Kuu is float32 (the
-    # front's interface) where the fused chain builds it in float64; measured (round 6): rel
-    # 1.8e-5 at cond(Kuu) 1.1e7, 1.2e-6 at 7.6e6, 5.3e-8 at BASELINE config 3 (cond 4.8e2)
-    rf = subprocess.run([BIN, str(prob), "--front"], capture_output=True, text=True, timeout=120)
-    assert rf.returncode == 0, rf.stdout + rf.stderr
-    lf = dict(l.split(" ", 1) for l in rf.stdout.strip().splitlines())
-    assert lf["info"].split() == ["0", "0"]
-    elbo_front = float(lf["elbo"])
-    cond = max(np.linalg.cond(R.rbf_Kuu(L["Z"], L["variance"], L["lengthscales"])) for L in (p.pred, p.assign))
-    print(f"front {elbo_front:.9g} (rel {abs(elbo_front - ref) / abs(ref):.2e}, cond(Kuu) {cond:.2e})")
-    assert elbo_front == pytest.approx(ref, rel=1e-4)

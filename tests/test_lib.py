@@ -37,6 +37,24 @@ def test_status_strings_and_argument_checks():
     assert lib.mgp_stats_tiles(1024) in (8, 16)   # 128- or 64-row tiles
 
 
+def test_size_limits_are_refused_and_documented():
+    """One past a size limit an entry returns MGP_ERR_UNSUPPORTED (3) before any HIP call or
+    pointer read (so this runs without a GPU; tests/test_gpu_range_edges.py covers every entry
+    on the device), and the header and INTEGRATION.md state the limits the code enforces."""
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.addressof(buf)     # never dereferenced: the calls below are refused first
+    assert lib.mgp_rbf_kuf(p, 33, p, 33, 10, 10, 33, p, p, 1, p, 12, None) == 3              # D <= 32
+    assert lib.mgp_trsm_stats(p, 4, p, 4, 4, 4, p, 20, 17, p, 4, p, 4, None) == 3            # K4: K <= 16
+    assert lib.mgp_relaxed_onehot_sample(p, 10, 33, 2, 0.01, None, 0, 0, p, None) == 3       # K6: K <= 32
+    assert b"supported range" in lib.mgp_status_string(3)
+    header = open(_lib.HEADER_PATH).read()
+    assert "D > 64" not in header
+    assert "D > 32" in header and "K > 16" in header and "K > 32" in header
+    doc = open(os.path.join(os.path.dirname(_lib.HEADER_PATH), "..", "INTEGRATION.md")).read()
+    assert "`D <= 32`" in doc and "`K <= 16`" in doc and "`K <= 32`" in doc
+
+
 def test_product_path_fails_loudly_without_library(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "missing.so"))
