@@ -29,7 +29,8 @@
  *    written; each entry's comment repeats its own):
  *      input dimension D <= 32: mgp_rbf_kuf, mgp_rbf_kuu (mgp_rbf_kuu_jitter),
  *        mgp_rbf_kuf_x6 / _f16, the Kuf side job of mgp_kuu_potrf_trtri_kuf,
- *        mgp_rbf_backward / _batch, mgp_full_cov_conditional;
+ *        mgp_rbf_backward / _batch, mgp_full_cov_conditional, mgp_vq, mgp_kmeans_* (these
+ *        also N <= 2^31 - 1, k <= N and R <= 64 runs);
  *      D unbounded: mgp_kuu_potrf_trtri / _ev / _ex (a generic Kuu build above D = 32);
  *      experts K <= 16: K4 (mgp_trsm_stats, _x6, _x6_f16, _f16, _f16x8, _f16_batch) and the
  *        conditional backward (mgp_conditional_backward_*, its _prep_f16c);
@@ -59,7 +60,7 @@ enum {
   MGP_ERR_WORKSPACE = 1,   /* workspace pointer NULL or too small */
   MGP_ERR_ALIGN = 2,       /* leading dimension / pointer alignment */
   MGP_ERR_UNSUPPORTED = 3, /* size outside the supported range: D > 32, K > 16 (K4, conditional
-                              backward) or K > 32 -- see "Size limits" above */
+                              backward) or K > 32, a k-means size -- see "Size limits" above */
   MGP_ERR_HIP_BASE = 1000
 };
 
@@ -774,6 +775,55 @@ int mgp_mixture_predict(const float* mu_f, const float* var_f, const float* mu_a
 int mgp_mixture_density_grid(const float* mu_f, const float* var_f, int64_t ldf, const float* lik_var,
                              const float* weights, int64_t N, int32_t K, const float* y_grid, int32_t G,
                              float* density, int64_t ldd, mgp_stream_t stream);
+
+/* ---------------------------------------------------------------- k-means (csrc/kmeans.hip)
+ * scipy.cluster.vq on the device: the inducing-point initialisation of every reference
+ * demo, Z = kmeans(Xtrain, num_ind, seed=0)[0] (demos/demo_tf2.py:39).  obs [N][ldo >= D]
+ * and code books [k][ld >= D] are float32 row-major (no alignment requirement).  Distances
+ * are sum_d (x_d - c_d)^2 on the float32 differences; the minimum is the first minimum
+ * (ties go to the lowest index); cluster sums and the mean distance are float64 in a fixed
+ * order (no floating-point atomics), so two calls return the same bits.
+ * Limits, MGP_ERR_UNSUPPORTED one past them before anything is launched or written:
+ * D <= 32, N <= 2^31 - 1, k <= N (mgp_vq: k <= 2^31 - 1), R <= 64 runs.
+ *
+ * mgp_vq replaces scipy.cluster.vq.vq(obs, code_book): code[n] = argmin_j |obs_n - c_j|^2
+ * (int32), dist[n] = sqrt of that minimum.  N == 0: MGP_OK, nothing done. */
+int mgp_vq(const float* obs, int64_t ldo, const float* code_book, int64_t ldc, int64_t N, int64_t k, int32_t D,
+           int32_t* code, float* dist, mgp_stream_t stream);
+/* The workspace of R runs (restarts) of k codes on N points; 0 outside the limits.  It holds
+ * the runs' state between the calls below and must be 16-B aligned. */
+size_t mgp_kmeans_workspace_bytes(int64_t N, int64_t k, int32_t D, int32_t R);
+/* Start R runs (scipy.cluster.vq._kpoints: guess = obs[rng.choice(N, k, replace=False)]):
+ * run r starts from the rows obs[idx[r][j]], idx a DEVICE int64 array [R][k] drawn by the
+ * caller; or one run (R == 1) from guess [k][ldg] (kmeans with an array k_or_guess).
+ * Exactly one of idx / guess is given (-5: neither, -6: both); -9: R < 1, or R != 1 with a
+ * guess. */
+int mgp_kmeans_init(const float* obs, int64_t ldo, int64_t N, int32_t D, const int64_t* idx, const float* guess,
+                    int64_t ldg, int64_t k, int32_t R, void* workspace, size_t workspace_bytes,
+                    mgp_stream_t stream);
+/* B Lloyd iterations of the R runs in lockstep (the loop body of scipy.cluster.vq._kmeans:
+ * vq, mean of the distances, update_cluster_means, code_book[has_members],
+ * diff = |avg_prev - avg|).  A run stops once diff <= thresh (its done flag; a stopped run
+ * costs nothing in later launches), so the result does not depend on B.  done: DEVICE
+ * int32 [R], written by every iteration for the runs still going -- the only thing the
+ * host reads back between blocks.  -7: B < 1; -8: thresh is NaN. */
+int mgp_kmeans_iterate(const float* obs, int64_t ldo, int64_t N, int32_t D, int64_t k, int32_t R, int32_t B,
+                       double thresh, void* workspace, size_t workspace_bytes, int32_t* done,
+                       mgp_stream_t stream);
+/* The restart selection of scipy.cluster.vq.kmeans (if dist < best_dist): the first run
+ * with the strictly smallest distortion.  code_book [k][ldcb]: its first info[0] rows are
+ * written; *distortion: the mean distance under the code book before the last update, as
+ * SciPy returns it; info (int32 [4]) = surviving codes k_active, winning run, its
+ * iterations, its done flag. */
+int mgp_kmeans_select(int64_t N, int64_t k, int32_t D, int32_t R, const void* workspace, size_t workspace_bytes,
+                      float* code_book, int64_t ldcb, double* distortion, int32_t* info, mgp_stream_t stream);
+/* One update from given labels (scipy.cluster.vq._vq.update_cluster_means): means[c] =
+ * float64 mean of the rows with code[n] == c (zeros for a code without members),
+ * counts[c] (int32) its members.  Labels outside [0, k) own nothing.  Workspace:
+ * mgp_kmeans_workspace_bytes(N, k, D, 1). */
+int mgp_kmeans_update(const float* obs, int64_t ldo, int64_t N, int32_t D, const int32_t* code, int64_t k,
+                      float* means, int64_t ldm, int32_t* counts, void* workspace, size_t workspace_bytes,
+                      mgp_stream_t stream);
 
 /* ---------------------------------------------------------------- optimizer
  * KL gradient folded into the ELBO gradient: g_q_mu -= q_mu / num_data,

@@ -231,6 +231,17 @@ SIGNATURES = {
                                            c_ptr, c_size, c_ptr]),
     "mgp_mixture_density_grid": (ctypes.c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_i32,
                                                 c_ptr, c_i64, c_ptr]),
+    # scipy.cluster.vq on the device (csrc/kmeans.hip)
+    "mgp_vq": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_ptr]),
+    "mgp_kmeans_workspace_bytes": (c_size, [c_i64, c_i64, c_i32, c_i32]),
+    "mgp_kmeans_init": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_i64, c_i64, c_i32, c_ptr, c_size,
+                                       c_ptr]),
+    "mgp_kmeans_iterate": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_i64, c_i32, c_i32, ctypes.c_double, c_ptr,
+                                          c_size, c_ptr, c_ptr]),
+    "mgp_kmeans_select": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, c_ptr, c_size, c_ptr, c_i64, c_ptr, c_ptr,
+                                         c_ptr]),
+    "mgp_kmeans_update": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr,
+                                         c_size, c_ptr]),
 }
 
 _lib = None

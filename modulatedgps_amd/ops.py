@@ -1242,3 +1242,92 @@ def mixture_density_grid(mu_f, var_f, lik_var, weights, y_grid):
     _lib.call("mgp_mixture_density_grid", mu_f.data_ptr(), var_f.data_ptr(), _ld(mu_f), lik_var.data_ptr(),
               weights.data_ptr(), N, K, y_grid.data_ptr(), G, out.data_ptr(), max(G, 1), _stream())
     return out
+
+
+# --------------------------------------------------------------------------- k-means
+I32 = torch.int32
+
+
+def _rows(t, name):
+    """A float32 device matrix whose rows are contiguous (any row stride >= D)."""
+    _check(t, name, 2)
+    if t.shape[1] > 1 and t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        t = t.contiguous()
+    return t, (t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1))
+
+
+def vq(obs, code_book, code=None, dist=None):
+    """scipy.cluster.vq.vq on the device (mgp_vq): code int32 [N] (first minimum of the
+    squared distances on float32 differences), dist float32 [N]."""
+    obs, ldo = _rows(obs, "obs")
+    code_book, ldc = _rows(code_book, "code_book")
+    N, D = obs.shape
+    k = code_book.shape[0]
+    if code_book.shape[1] != D:
+        raise ValueError("obs and code_book must have the same number of features")
+    code = torch.empty(N, dtype=I32, device=obs.device) if code is None else code
+    dist = torch.empty(N, dtype=F32, device=obs.device) if dist is None else dist
+    _lib.call("mgp_vq", obs.data_ptr(), ldo, code_book.data_ptr(), ldc, N, k, D, code.data_ptr(), dist.data_ptr(),
+              _stream())
+    return code, dist
+
+
+def kmeans_workspace(N, k, D, R, device):
+    nbytes = _lib.load().mgp_kmeans_workspace_bytes(N, k, D, R)
+    if nbytes == 0:
+        _lib.check("mgp_kmeans_workspace_bytes", 3)
+    return _ws(nbytes, device)
+
+
+def kmeans_init(obs, k, workspace, idx=None, guess=None):
+    """Start R runs from the rows obs[idx[r]] (idx: device int64 [R, k]) or one run from
+    guess [k, D] (mgp_kmeans_init)."""
+    obs, ldo = _rows(obs, "obs")
+    N, D = obs.shape
+    R, gp, ldg, ip = 1, None, 0, None
+    if guess is not None:
+        guess, ldg = _rows(guess, "guess")
+        gp = guess.data_ptr()
+    if idx is not None:
+        if idx.dtype != torch.int64 or not idx.is_cuda or idx.dim() != 2 or idx.shape[1] != k:
+            raise ValueError("idx must be a device int64 tensor [R, k]")
+        idx = idx.contiguous()
+        R, ip = idx.shape[0], idx.data_ptr()
+    _lib.call("mgp_kmeans_init", obs.data_ptr(), ldo, N, D, ip, gp, ldg, k, R, workspace.data_ptr(),
+              workspace.numel(), _stream())
+    return R
+
+
+def kmeans_iterate(obs, k, R, B, thresh, workspace, done):
+    """B Lloyd iterations of the R runs of the workspace (mgp_kmeans_iterate); done: device
+    int32 [R]."""
+    obs, ldo = _rows(obs, "obs")
+    N, D = obs.shape
+    _lib.call("mgp_kmeans_iterate", obs.data_ptr(), ldo, N, D, k, R, int(B), float(thresh), workspace.data_ptr(),
+              workspace.numel(), done.data_ptr(), _stream())
+
+
+def kmeans_select(N, k, D, R, workspace, result):
+    """The winning run into `result`, a device uint8 buffer laid out as
+    [float64 distortion | int32 info[4] | pad to 32 B | float32 code_book [k, D]]
+    (mgp_kmeans_select), so that one copy brings everything to the host."""
+    base = result.data_ptr()
+    _lib.call("mgp_kmeans_select", N, k, D, R, workspace.data_ptr(), workspace.numel(), base + 32, D, base,
+              base + 8, _stream())
+
+
+def kmeans_update(obs, code, k, workspace=None):
+    """One update from given labels (mgp_kmeans_update): means float32 [k, D] (zeros for a
+    code without members), counts int32 [k]."""
+    obs, ldo = _rows(obs, "obs")
+    N, D = obs.shape
+    if code.dtype != I32 or not code.is_cuda or code.numel() != N:
+        raise ValueError("code must be a device int32 tensor [N]")
+    code = code.contiguous()
+    if workspace is None:
+        workspace = kmeans_workspace(N, k, D, 1, obs.device)
+    means = torch.empty(k, D, dtype=F32, device=obs.device)
+    counts = torch.empty(k, dtype=I32, device=obs.device)
+    _lib.call("mgp_kmeans_update", obs.data_ptr(), ldo, N, D, code.data_ptr(), k, means.data_ptr(), D,
+              counts.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream())
+    return means, counts
