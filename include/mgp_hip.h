@@ -40,7 +40,8 @@
  *        mgp_expert_conditional;
  *      K unbounded: K5 on given statistics (mgp_expert_conditional_f32 / _x6 / _planes /
  *        _f16*), the image splits, mgp_gauss_kl_white, mgp_predict_epilogue,
- *        mgp_assign_logits, mgp_philox_noise / _normal2.
+ *        mgp_assign_logits, mgp_philox_noise / _normal2; mgp_natgrad_step up to its grid
+ *        limit (K <= 65535, and M <= 2^20).
  *    So the one chain that runs K in 17 .. 32 end to end is the SURVEY 8(b) front.
  */
 #ifndef MGP_HIP_H
@@ -849,6 +850,42 @@ int mgp_adam_step_set(int32_t n, float* const* theta, float* const* u, const voi
                       const int32_t* grad_is_double, const int64_t* ldg, float* const* m1, float* const* m2,
                       const int64_t* rows, const int64_t* cols, const int64_t* ld, float lr, float beta1,
                       float beta2, float eps, int64_t t, float grad_sign, mgp_stream_t stream);
+
+/* One natural-gradient step on the variational parameters of a whitened layer
+ * (gpflow.optimizers.NaturalGradient(gamma).minimize(loss, var_list=[(q_mu, q_sqrt)]) with
+ * the XiSqrtMeanVar parameterisation, run beside Adam on the hyper-parameters;
+ * csrc/natgrad.hip).  Per expert k, with L = band_part(q_sqrt[k], -1, 0), mu = q_mu[:, k] and
+ * g = grad_sign * (g_q_mu, g_q_sqrt) the gradients of the loss being minimised (grad_sign as
+ * in mgp_adam_step: -1 for the ELBO gradients of the training step; g_q_sqrt is read below
+ * and on the diagonal only):
+ *   P = Phi(L^T g_L) (lower triangle, diagonal halved),  B = I + step (P + P^T),
+ *   B = W^T W (W lower, from the Cholesky factor of the index-flipped B),
+ *   L' = L W^-1,  mu' = mu - step L' (L'^T g_mu),
+ * which is theta <- theta - step d loss / d eta for the natural parameters theta =
+ * (S^-1 mu, -S^-1 / 2) and the expectation parameters eta = (mu, S + mu mu^T), S = L L^T.
+ * Float64 arithmetic on the float32 inputs (K3 factorises B without a float32 rounding);
+ * q_mu and tril(q_sqrt[k]) are overwritten, rounded to float32 once; q_sqrt above the
+ * diagonal is not touched; sign(diag L') = sign(diag L).
+ * info[k] (device int32 [K]) = 0, or, when B is not positive definite, the 1-based column of
+ * the first non-positive pivot of the flipped B (LAPACK potrf convention, as K3): expert k's
+ * q_mu column and q_sqrt[k] then stay bitwise unchanged and the other experts are updated as
+ * normal -- no NaN is ever written to the parameters.  step == 0: info = 0 and the
+ * parameters stay bitwise unchanged.  Fixed summation orders, no floating-point atomics: two
+ * calls give the same bits.
+ * q_mu [M][ldq >= K], q_sqrt [K][M][ldqs >= M] at element stride strideq; g_q_mu [M][ldg >= K],
+ * g_q_sqrt [K][M][ldgs >= M] at element stride strideg, both float (grad_is_double = 0) or both
+ * double (1).  Any M >= 1 and K >= 1 (M <= 2^20, K <= 65535: MGP_ERR_UNSUPPORTED beyond).
+ * Workspace: mgp_natgrad_workspace_bytes(M, K) (0 outside the limits), 16-B aligned.
+ * -1 q_mu, -2 ldq < K, -3 q_sqrt, -4 ldqs < M, -5 strideq < ldqs M (K > 1), -6 g_q_mu,
+ * -7 ldg < K, -8 g_q_sqrt, -9 ldgs < M, -10 strideg < ldgs M (K > 1), -11 grad_is_double not
+ * 0 / 1, -12 M < 1, -13 K < 1, -14 step negative or not finite, -15 grad_sign not finite,
+ * -16 info; a NULL or short workspace: MGP_ERR_WORKSPACE; all checked before any pointer is
+ * read or HIP call made. */
+size_t mgp_natgrad_workspace_bytes(int64_t M, int32_t K);
+int mgp_natgrad_step(float* q_mu, int64_t ldq, float* q_sqrt, int64_t ldqs, int64_t strideq,
+                     const void* g_q_mu, int64_t ldg, const void* g_q_sqrt, int64_t ldgs, int64_t strideg,
+                     int32_t grad_is_double, int64_t M, int32_t K, float step, float grad_sign, int32_t* info,
+                     void* workspace, size_t workspace_bytes, mgp_stream_t stream);
 
 
 /* ---------------------------------------------------------------- the §8(b) front

@@ -927,6 +927,50 @@ __global__ __launch_bounds__(kCholThreads) void chol_prep(CholArgs a) {
   }
 }
 
+// chol_prep for a float64 input: batch entry b is the symmetric matrix Ad + b strideAd
+// ([M][ldad] doubles, read in full precision -- the natural-gradient step's B, natgrad.hip).
+// The same launch shape and the same work per workgroup as chol_prep's generic path: tile
+// (0, 0) factored from the input, the lower tiles of W, the zero fills of L / L^-T.
+__global__ __launch_bounds__(kCholThreads) void chol_prep_f64(CholArgs a, const double* __restrict__ Ad,
+                                                              int64_t ldad, int64_t strideAd) {
+  __shared__ double s1[CB * LDT], s2[CB * LDT], col[CB];
+  const int b = blockIdx.y;
+  const double* Ab = Ad + (int64_t)b * strideAd;
+  auto elem = [&](int64_t gr, int64_t gc) {
+    if (gr >= a.M || gc >= a.M) return gr == gc ? 1.0 : 0.0;
+    return Ab[gr * ldad + gc];
+  };
+  if (blockIdx.x == 0) {
+    if (threadIdx.x == 0) a.info[b] = 0;
+    for (int idx = threadIdx.x; idx < CB * CB; idx += kCholThreads) {
+      const int r = idx >> 6, c = idx & 63;
+      s1[r * LDT + c] = elem(r, c);
+    }
+    __syncthreads();
+    factor_diag_tile(s1, s2, col, a.info + b, 0);
+    __syncthreads();
+    write_diag(a, b, 0, s1, s2);
+    return;
+  }
+  const int bi = (blockIdx.x - 1) / a.nb, bl = (blockIdx.x - 1) % a.nb;
+  const int64_t r0 = (int64_t)bi * CB, c0 = (int64_t)bl * CB;
+  if (bl <= bi) {
+    double* dst = ws_tile(a, ws_W(a, b), bi, bl);
+    for (int idx = threadIdx.x; idx < CB * CB; idx += kCholThreads) {
+      const int r = idx >> 6, c = idx & 63;
+      dst[r * CB + c] = elem(r0 + r, c0 + c);
+    }
+  }
+  if (bl != bi && (bl < bi || a.L)) {
+    float* dst = (bl > bi ? a.L : a.LinvT) + (int64_t)b * a.strideL;
+    for (int idx = threadIdx.x; idx < CB * CB; idx += kCholThreads) {
+      const int r = idx >> 6, c = idx & 63;
+      const int64_t gr = r0 + r, gc = c0 + c;
+      if (gr < a.M && gc < a.M) dst[gr * a.ldl + gc] = 0.f;
+    }
+  }
+}
+
 // ------------------------------------------------------------------ step launch j
 // The look-ahead's factorisation of tile (j+1, j+1): s1 holds P = L_{j+1,j}, s2 the
 // tile with column block 0 of -P P^T still to apply.
@@ -1464,7 +1508,8 @@ static void kuf_side_split(int nb, int batch, int64_t total, std::vector<int64_t
 }
 
 static int chol_run(CholArgs& a, int batch, void* workspace, size_t workspace_bytes, hipStream_t s,
-                    hipEvent_t prep_done = nullptr, const KufSideJob* kj = nullptr) {
+                    hipEvent_t prep_done = nullptr, const KufSideJob* kj = nullptr, const double* Ad = nullptr,
+                    int64_t ldad = 0, int64_t strideAd = 0) {
   if (!workspace || workspace_bytes < mgp_chol_workspace_bytes(a.M, batch)) return MGP_ERR_WORKSPACE;
   if (!aligned16(workspace)) return MGP_ERR_ALIGN;
   // the diagonal tiles of L and L^-T are written with 16-byte stores
@@ -1489,7 +1534,11 @@ static int chol_run(CholArgs& a, int batch, void* workspace, size_t workspace_by
     }
     if (a.nb >= 2) kuf_side_split(a.nb, batch, batch * a.kblocks, kbeg, knwg, s);
   }
-  hipLaunchKernelGGL(chol_prep, dim3(a.nb * a.nb + 1, batch), block, 0, s, a);
+  if (Ad) {
+    hipLaunchKernelGGL(chol_prep_f64, dim3(a.nb * a.nb + 1, batch), block, 0, s, a, Ad, ldad, strideAd);
+  } else {
+    hipLaunchKernelGGL(chol_prep, dim3(a.nb * a.nb + 1, batch), block, 0, s, a);
+  }
   int st = launch_status();
   if (st) return st;
   if (prep_done) {
@@ -1541,6 +1590,18 @@ extern "C" int mgp_potrf_trtri(const float* A, int64_t lda, int64_t strideA, int
   a.L = L; a.LinvT = LinvT; a.ldl = ldl; a.strideL = strideL;
   a.info = info; a.M = M;
   return chol_run(a, batch, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// mgp_potrf_trtri on float64 input matrices Ad + b strideAd ([M][ldad], symmetric), for the
+// library's own callers (natgrad.hip); declared in mgp_common.hpp.  No L output.
+int mgp::mgp_potrf_trtri_f64(const double* Ad, int64_t ldad, int64_t strideAd, int64_t M, int batch, float* LinvT,
+                             int64_t ldl, int64_t strideL, int32_t* info, void* workspace, size_t workspace_bytes,
+                             hipStream_t s) {
+  if (batch < 1 || batch > kMaxBatch || M < 1) return MGP_ERR_UNSUPPORTED;
+  CholArgs a = {};
+  a.LinvT = LinvT; a.ldl = ldl; a.strideL = strideL;
+  a.info = info; a.M = M;
+  return chol_run(a, batch, workspace, workspace_bytes, s, nullptr, nullptr, Ad, ldad, strideAd);
 }
 
 static int kuu_potrf_trtri_impl(const float* const* Z, int64_t ldz, int64_t M, int32_t D,

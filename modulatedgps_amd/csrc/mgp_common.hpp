@@ -37,6 +37,13 @@ struct CondFinLayer {
 int mgp_launch_cond_finalize2(const CondFinLayer& l0, const CondFinLayer& l1, int64_t lds, int nTs, int64_t ldp,
                               int nTp, int64_t N, int K, int64_t ldf, hipStream_t s);
 
+// K3 (chol.hip) on float64 input: info[b] and LinvT[b] = (chol(A_b)^-1)^T as mgp_potrf_trtri
+// gives them, A_b = Ad + b strideAd ([M][ldad] doubles, symmetric) read without a float32
+// rounding.  1 <= batch <= 8; workspace mgp_chol_workspace_bytes(M, batch).
+int mgp_potrf_trtri_f64(const double* Ad, int64_t ldad, int64_t strideAd, int64_t M, int batch, float* LinvT,
+                        int64_t ldl, int64_t strideL, int32_t* info, void* workspace, size_t workspace_bytes,
+                        hipStream_t s);
+
 // ------------------------------------------------------------------ MFMA
 // D(32x32) += A(32x2) * B(2x32), exact f32 (fmaf chain).  Lane l supplies
 // A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31].  Result register r of

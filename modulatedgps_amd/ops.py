@@ -769,6 +769,43 @@ class AdamSet:
                   int(t), float(grad_sign), _stream())
 
 
+def natgrad_workspace(M, K, device):
+    nbytes = _lib.load().mgp_natgrad_workspace_bytes(M, K)
+    if nbytes == 0:
+        _lib.check("mgp_natgrad_workspace_bytes", 3)
+    return _ws(nbytes, device)
+
+
+def natgrad_step(q_mu, q_sqrt, g_q_mu, g_q_sqrt, step, grad_sign=-1.0, info=None, workspace=None):
+    """One natural-gradient step (mgp_natgrad_step; gpflow.optimizers.NaturalGradient with
+    XiSqrtMeanVar) on q_mu [M, K] and q_sqrt [K, M, M], in place, from the gradients
+    g_q_mu [M, K] / g_q_sqrt [K, M, M] (both float32 or both float64; grad_sign -1: they are
+    the ELBO's, as elbo_and_grad returns them).  Returns info, device int32 [K]: 0, or the
+    pivot column where the step does not exist (that expert is left unchanged).  No
+    synchronisation with the host."""
+    _check(q_mu, "q_mu", 2), _check(q_sqrt, "q_sqrt", 3)
+    M, K = q_mu.shape
+    if tuple(q_sqrt.shape) != (K, M, M):
+        raise ValueError(f"q_sqrt must be [{K}, {M}, {M}], got {tuple(q_sqrt.shape)}")
+    if tuple(g_q_mu.shape) != (M, K) or tuple(g_q_sqrt.shape) != (K, M, M):
+        raise ValueError("gradient / parameter shape mismatch")
+    if g_q_mu.dtype != g_q_sqrt.dtype or g_q_mu.dtype not in (torch.float32, torch.float64):
+        raise ValueError("g_q_mu and g_q_sqrt must both be float32 or both float64")
+    for t, name in ((g_q_mu, "g_q_mu"), (g_q_sqrt, "g_q_sqrt")):
+        if not t.is_cuda or t.device != q_mu.device:
+            raise ValueError(f"{name} must be on {q_mu.device}")
+    if info is None:
+        info = torch.empty(K, dtype=torch.int32, device=q_mu.device)
+    nbytes = _lib.load().mgp_natgrad_workspace_bytes(M, K)
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = natgrad_workspace(M, K, q_mu.device)
+    _lib.call("mgp_natgrad_step", q_mu.data_ptr(), _ld(q_mu), q_sqrt.data_ptr(), _ld(q_sqrt), q_sqrt.stride(0),
+              g_q_mu.data_ptr(), _ld(g_q_mu), g_q_sqrt.data_ptr(), _ld(g_q_sqrt), g_q_sqrt.stride(0),
+              int(g_q_mu.dtype == torch.float64), M, K, float(step), float(grad_sign), info.data_ptr(),
+              workspace.data_ptr(), workspace.numel(), _stream())
+    return info
+
+
 def gram(X, Y, N=None, alpha=1.0, tri=False, out=None, workspace=None):
     """out[i][j] = alpha * sum_n X[i][n] Y[j][n] (tri: lower triangle, zeros above)."""
     _check(X, "X", 2), _check(Y, "Y", 2)

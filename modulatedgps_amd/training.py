@@ -24,6 +24,46 @@ def _as2d(t):
     return t
 
 
+NATGRAD_BLOCKS = ("pred.q_mu", "pred.q_sqrt", "assign.q_mu", "assign.q_sqrt")
+
+
+class NaturalGradient:
+    """gpflow.optimizers.NaturalGradient(gamma) on (q_mu, q_sqrt) of both SVGP layers
+    (XiSqrtMeanVar; ops.natgrad_step, csrc/natgrad.hip), used beside AdamTF on the other
+    blocks.  The model's loss is the per-datum ELBO (data mean - KL / num_data), so the
+    kernel's step is gamma * scale with scale = model.num_data by default: gamma then has
+    the meaning it has for GPflow's total-ELBO loss, and gamma = 1 solves a conjugate model
+    in one step.  An expert whose step does not exist (info != 0) is left as it is and
+    counted on the device; skipped() reads the count (a host sync: readback points only)."""
+
+    def __init__(self, gamma, scale=None):
+        self.gamma = float(gamma)
+        self.scale = None if scale is None else float(scale)
+        self._skipped = None
+        self._ws = {}
+
+    def step(self, model, grads):
+        """Apply one step to both layers from the ELBO gradients (dict name -> tensor)."""
+        scale = self.scale if self.scale is not None else model.num_data
+        if scale is None:
+            raise ValueError("NaturalGradient needs scale= or a model with num_data set")
+        infos = []
+        for name, layer in (("pred", model.pred_layer), ("assign", model.assign_layer)):
+            M, K = layer.q_mu.shape
+            key = (M, K, layer.q_mu.device)
+            if key not in self._ws:
+                self._ws[key] = ops.natgrad_workspace(M, K, layer.q_mu.device)
+            infos.append(ops.natgrad_step(layer.q_mu, layer.q_sqrt, grads[name + ".q_mu"], grads[name + ".q_sqrt"],
+                                          self.gamma * float(scale), grad_sign=-1.0, workspace=self._ws[key]))
+        n = sum((i != 0).sum() for i in infos)
+        self._skipped = n if self._skipped is None else self._skipped + n
+        return infos
+
+    def skipped(self):
+        """Expert steps skipped so far (synchronises with the device)."""
+        return 0 if self._skipped is None else int(self._skipped.cpu())
+
+
 class AdamTF:
     """tf.optimizers.Adam(lr) (beta1 0.9, beta2 0.999, epsilon 1e-7) over
     model.trainable_parameters()."""
