@@ -36,8 +36,8 @@
  *        conditional backward (mgp_conditional_backward_*, its _prep_f16c);
  *      experts K <= 32: K6 and its backward (mgp_elbo_terms*), mgp_relaxed_onehot_sample,
  *        mgp_e_log_p_y, mgp_predict_samples*, mgp_multiclass_predict,
- *        mgp_full_cov_conditional, mgp_mixture_predict / _density_grid and the front's
- *        mgp_expert_conditional;
+ *        mgp_full_cov_conditional, mgp_mixture_predict / _density_grid, mgp_mixture_score,
+ *        mgp_mixture_quantiles (also Q <= 256 levels) and the front's mgp_expert_conditional;
  *      K unbounded: K5 on given statistics (mgp_expert_conditional_f32 / _x6 / _planes /
  *        _f16*), the image splits, mgp_gauss_kl_white, mgp_predict_epilogue,
  *        mgp_assign_logits, mgp_philox_noise / _normal2; mgp_natgrad_step up to its grid
@@ -777,6 +777,44 @@ int mgp_mixture_density_grid(const float* mu_f, const float* var_f, int64_t ldf,
                              const float* weights, int64_t N, int32_t K, const float* y_grid, int32_t G,
                              float* density, int64_t ldd, mgp_stream_t stream);
 
+/* ---------------------------------------------------------------- mixture scores (csrc/mixture_score.hip)
+ * CDF, survival function, CRPS and quantiles of the mixture predictive above, from the
+ * latents and the weights [N][K] of mgp_mixture_predict (S == 0 plug-in or averaged over S
+ * draws; no noise is drawn here).  DESIGN "Mixture scores" is the specification.  Per point,
+ * with s_k = sqrt(var_f,k + lik_var_k) and t_k = (Y - mu_f,k) / s_k:
+ *   cdf[n]  = sum_k w_k erfc(-t_k / sqrt 2) / 2      (the PIT value F(y | x))
+ *   sf[n]   = sum_k w_k erfc(+t_k / sqrt 2) / 2      (its own sum, not 1 - cdf: accurate
+ *                                                      relative to the upper tail)
+ *   A(m, v) = m erf(m / sqrt(2 v)) + sqrt(2 v / pi) exp(-m^2 / (2 v))
+ *   crps[n] = sum_i w_i A(Y - mu_i, s_i^2) - 1/2 sum_i sum_j w_i w_j A(mu_i - mu_j, s_i^2 + s_j^2),
+ *             the pair sum as sum_i w_i^2 A(0, 2 s_i^2) + 2 sum_{i<j}, in a fixed order
+ *   crps_sum = sum_n crps[n]   (one double; deterministic two-stage sum of the float32 values)
+ * Latents expert-major [K][ldf >= N]; lik_var [K], Y [N] (device).  Per-point outputs do not
+ * depend on how N is sharded, and two calls return the same bits.  Every output may be NULL.
+ * The workspace (mgp_mixture_score_workspace_bytes(N, K), also mgp_workspace_bytes(
+ * MGP_OP_MIXTURE_SCORE, 0, N, K)) is used, and checked, only when crps_sum is not NULL.
+ * -1 mu_f, -2 var_f, -3 ldf < N, -4 lik_var, -5 weights, -6 Y, -8 K < 1; K > 32:
+ * MGP_ERR_UNSUPPORTED; all checked before any pointer is read or HIP call made.  N <= 0:
+ * MGP_OK after the checks, nothing done. */
+size_t mgp_mixture_score_workspace_bytes(int64_t N, int32_t K);
+int mgp_mixture_score(const float* mu_f, const float* var_f, int64_t ldf, const float* lik_var,
+                      const float* weights, const float* Y, int64_t N, int32_t K, float* cdf, float* sf,
+                      float* crps, double* crps_sum, void* workspace, size_t workspace_bytes,
+                      mgp_stream_t stream);
+/* quantiles[n][q] = the y with cdf(y) = levels[q] for a level <= 1/2 and with sf(y) =
+ * 1 - levels[q] above (the float32 subtraction, which is exact), so both tails are solved
+ * relative to the tail.  levels [Q] (device), quantiles [N][ldq >= Q] row-major.  A bracketed
+ * Newton iteration per (point, level): the bracket [min_k e_k, max_k e_k], e_k = mu_k + s_k
+ * Phi^-1(level), widened by 4e-6 (|e| + max_k s_k); the bisection point whenever the Newton
+ * iterate is not strictly inside the bracket or the bracket did not halve over the last two
+ * iterations; it stops on an exact hit or adjacent endpoints, at most 100 iterations.  A level
+ * outside (0, 1) or NaN gives NaN.  -1 mu_f, -2 var_f, -3 ldf < N, -4 lik_var, -5 weights,
+ * -7 K < 1, -8 levels, -9 Q < 0, -10 quantiles, -11 ldq < Q; K > 32 or Q > 256:
+ * MGP_ERR_UNSUPPORTED.  N <= 0 or Q == 0: MGP_OK after the checks, nothing done. */
+int mgp_mixture_quantiles(const float* mu_f, const float* var_f, int64_t ldf, const float* lik_var,
+                          const float* weights, int64_t N, int32_t K, const float* levels, int32_t Q,
+                          float* quantiles, int64_t ldq, mgp_stream_t stream);
+
 /* ---------------------------------------------------------------- k-means (csrc/kmeans.hip)
  * scipy.cluster.vq on the device: the inducing-point initialisation of every reference
  * demo, Z = kmeans(Xtrain, num_ind, seed=0)[0] (demos/demo_tf2.py:39).  obs [N][ldo >= D]
@@ -908,7 +946,8 @@ enum {
   MGP_OP_CHOL_BACKWARD = 10,
   MGP_OP_RBF_BACKWARD = 11,
   MGP_OP_FULL_COV_CONDITIONAL = 12,
-  MGP_OP_MIXTURE_PREDICT = 13
+  MGP_OP_MIXTURE_PREDICT = 13,
+  MGP_OP_MIXTURE_SCORE = 14
 };
 size_t mgp_workspace_bytes(int32_t op, int64_t M, int64_t N, int32_t K);
 /* Kuu = K(Z, Z) + jitter I in float32 (covariances.Kuu, models.py:135); same as

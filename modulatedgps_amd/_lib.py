@@ -231,6 +231,12 @@ SIGNATURES = {
                                            c_ptr, c_size, c_ptr]),
     "mgp_mixture_density_grid": (ctypes.c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_i32,
                                                 c_ptr, c_i64, c_ptr]),
+    # CDF, CRPS and quantiles of the mixture predictive (csrc/mixture_score.hip)
+    "mgp_mixture_score_workspace_bytes": (c_size, [c_i64, c_i32]),
+    "mgp_mixture_score": (ctypes.c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr,
+                                         c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "mgp_mixture_quantiles": (ctypes.c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_i32, c_ptr,
+                                             c_i64, c_ptr]),
     # natural-gradient step on (q_mu, q_sqrt) (csrc/natgrad.hip)
     "mgp_natgrad_workspace_bytes": (c_size, [c_i64, c_i32]),
     "mgp_natgrad_step": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64,

@@ -125,6 +125,8 @@ extern "C" size_t mgp_workspace_bytes(int32_t op, int64_t M, int64_t N, int32_t 
       return mgp_full_cov_workspace_bytes(M, N, K);
     case MGP_OP_MIXTURE_PREDICT:
       return mgp_mixture_predict_workspace_bytes(N, K);
+    case MGP_OP_MIXTURE_SCORE:
+      return mgp_mixture_score_workspace_bytes(N, K);
     default:
       return 0;
   }

@@ -1346,6 +1346,78 @@ class SMGP(SGP):
         self.check_linalg()
         return float(v.cpu())
 
+    # ------------------------------------------------------------------ mixture scores
+    # CDF / PIT values, quantiles and CRPS of the mixture predictive above (DESIGN "Mixture
+    # scores"): one conditionals(X), one mgp_mixture_predict for the weights (S, noise_z and seed
+    # as in the methods above) and one mgp_mixture_score or mgp_mixture_quantiles on them.
+    def _score(self, Xnew, Ynew, S, want, noise_z=None, seed=None, n_offset=0):
+        if Ynew is None:
+            raise ValueError("Ynew is required")
+        out, (mu_f, var_f, lik_var) = self._mixture(Xnew, S, ("weights",), Y=Ynew, noise_z=noise_z, seed=seed,
+                                                    n_offset=n_offset)
+        Yd = _to_dev(Ynew, self.device).reshape(-1).contiguous()
+        return ops.mixture_score(mu_f, var_f, lik_var, out["weights"], Yd, want=want), mu_f.shape[1]
+
+    def predict_cdf_device(self, Xnew, Ynew, S=0, noise_z=None, seed=None, tail="lower"):
+        """predict_cdf as a float32 device tensor [N]."""
+        if tail not in ("lower", "upper"):
+            raise ValueError("tail must be 'lower' or 'upper'")
+        name = "cdf" if tail == "lower" else "sf"
+        return self._score(Xnew, Ynew, S, (name,), noise_z=noise_z, seed=seed)[0][name]
+
+    def predict_cdf(self, Xnew, Ynew, S=0, noise_z=None, seed=None, tail="lower"):
+        """F(Ynew | Xnew) of the mixture predictive per point, [N] (HostArray, float64): the
+        probability integral transform values of a calibration histogram.  tail="upper": the
+        survival function 1 - F as its own sum, accurate relative to the upper tail."""
+        c = self.predict_cdf_device(Xnew, Ynew, S, noise_z=noise_z, seed=seed, tail=tail)
+        self.check_linalg()
+        return _host(c)
+
+    def predict_quantiles_device(self, Xnew, levels, S=0, noise_z=None, seed=None):
+        """predict_quantiles as a float32 device tensor [N, Q]."""
+        lv = ops.quantile_levels(levels)   # ValueError before anything runs
+        out, (mu_f, var_f, lik_var) = self._mixture(Xnew, S, ("weights",), noise_z=noise_z, seed=seed)
+        return ops.mixture_quantiles(mu_f, var_f, lik_var, out["weights"], lv)
+
+    def predict_quantiles(self, Xnew, levels, S=0, noise_z=None, seed=None):
+        """Quantiles of the mixture predictive, [N, Q] (HostArray, float64), e.g. levels
+        [0.025, 0.5, 0.975] for a credible band that follows a multimodal predictive where
+        mean +- 2 sd cannot.  Levels lie strictly inside (0, 1) (ValueError otherwise)."""
+        q = self.predict_quantiles_device(Xnew, levels, S, noise_z=noise_z, seed=seed)
+        self.check_linalg()
+        return _host(q)
+
+    def predict_crps_device(self, Xnew, Ynew, S=0, noise_z=None, seed=None):
+        """predict_crps as a float32 device tensor [N]."""
+        return self._score(Xnew, Ynew, S, ("crps",), noise_z=noise_z, seed=seed)[0]["crps"]
+
+    def predict_crps(self, Xnew, Ynew, S=0, noise_z=None, seed=None):
+        """The continuous ranked probability score of the mixture predictive at Ynew per point,
+        [N] (HostArray, float64), in closed form (lower is better; the units of y)."""
+        c = self.predict_crps_device(Xnew, Ynew, S, noise_z=noise_z, seed=seed)
+        self.check_linalg()
+        return _host(c)
+
+    def crps_device(self, X, Y, S=0, noise_z=None, seed=None, n_offset=0, n_total=None, process_group=None):
+        """crps as a 0-d float64 device tensor (no host sync)."""
+        out, N = self._score(X, Y, S, ("crps_sum",), noise_z=noise_z, seed=seed, n_offset=n_offset)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        sc = torch.cat([out["crps_sum"], torch.full((1,), float(N), **f64)])
+        if process_group is not None:
+            import torch.distributed as dist
+            dist.all_reduce(sc, op=dist.ReduceOp.SUM, group=process_group)
+        # a tensor divisor in every case, as in log_predictive_density_device
+        return sc[0] / (sc[1] if n_total is None else torch.full((), float(n_total), **f64))
+
+    def crps(self, X, Y, S=0, noise_z=None, seed=None, n_offset=0, n_total=None, process_group=None):
+        """Mean CRPS over all points, a Python float from the float64 sum of the per-point
+        values; sharded over N exactly as log_predictive_density (n_offset / n_total /
+        process_group: one all-reduce of [sum, count])."""
+        v = self.crps_device(X, Y, S, noise_z=noise_z, seed=seed, n_offset=n_offset, n_total=n_total,
+                             process_group=process_group)
+        self.check_linalg()
+        return float(v.cpu())
+
 
 class SMGPModified(SMGP):
     """SMGP with a second (assignment) Gaussian likelihood on the assign layer

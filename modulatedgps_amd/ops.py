@@ -10,6 +10,8 @@ dimensions padded to a multiple of 4 elements so rows can be read as float4.
 outputs are [K][N] views.
 """
 import ctypes
+
+import numpy as np
 import torch
 
 from . import _lib
@@ -1278,6 +1280,100 @@ def mixture_density_grid(mu_f, var_f, lik_var, weights, y_grid):
     out = torch.empty(N, G, dtype=F32, device=mu_f.device)
     _lib.call("mgp_mixture_density_grid", mu_f.data_ptr(), var_f.data_ptr(), _ld(mu_f), lik_var.data_ptr(),
               weights.data_ptr(), N, K, y_grid.data_ptr(), G, out.data_ptr(), max(G, 1), _stream())
+    return out
+
+
+# --------------------------------------------------------------------------- mixture scores
+SCORE_OUTPUTS = ("cdf", "sf", "crps", "crps_sum")
+MAX_LEVELS = 256
+
+
+def mixture_score(mu_f, var_f, lik_var, weights, Y, want=None, workspace=None, out=None):
+    """CDF, survival function and CRPS of the mixture predictive at the targets Y
+    (mgp_mixture_score, csrc/mixture_score.hip), from mixture_predict's weights [N, K] -> dict
+    of the outputs named in `want` (default: all): cdf [N] (the PIT values), sf [N] (its own
+    erfc sum, accurate in the upper tail), crps [N] (float32) and crps_sum [1] (float64).
+    out: a dict of an earlier call at the same shapes, whose tensors are written again."""
+    _latents_check(mu_f, var_f, "f")
+    K, N = mu_f.shape
+    dev = mu_f.device
+    _check(lik_var, "lik_var"), _check(weights, "weights", 2)
+    if tuple(weights.shape) != (N, K):
+        raise ValueError("weights must be [N, K]")
+    weights = weights.contiguous()
+    Y = Y.reshape(-1)
+    _check(Y, "Y")
+    if Y.numel() != N or not Y.is_contiguous():
+        raise ValueError("Y must be contiguous with N elements")
+    want = SCORE_OUTPUTS if want is None else want
+    unknown = [w for w in want if w not in SCORE_OUTPUTS]
+    if unknown:
+        raise ValueError(f"unknown outputs {unknown}; choose from {SCORE_OUTPUTS}")
+    have, out = out or {}, {}
+    for name in want:
+        shape, dtype = ((1,), torch.float64) if name == "crps_sum" else ((N,), F32)
+        t = have.get(name)
+        if t is not None:
+            if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"out[{name!r}] must be a contiguous {dtype} tensor of shape {shape}")
+        elif name == "crps_sum" and N == 0:
+            t = torch.zeros(shape, dtype=dtype, device=dev)   # the entry does nothing for N = 0
+        else:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        out[name] = t
+    wp = wb = None
+    if "crps_sum" in out:
+        nbytes = _lib.load().mgp_mixture_score_workspace_bytes(N, K)
+        if workspace is None or workspace.numel() < nbytes:
+            workspace = _ws(nbytes, dev)
+        wp, wb = workspace.data_ptr(), workspace.numel()
+    ptr = lambda name: out[name].data_ptr() if name in out else None
+    _lib.call("mgp_mixture_score", mu_f.data_ptr(), var_f.data_ptr(), _ld(mu_f), lik_var.data_ptr(),
+              weights.data_ptr(), Y.data_ptr(), N, K, *[ptr(n) for n in SCORE_OUTPUTS], wp, wb or 0, _stream())
+    return out
+
+
+def quantile_levels(levels):
+    """The levels as a float32 host array [Q], each inside (0, 1) after the rounding to
+    float32 (ValueError otherwise, before anything is uploaded)."""
+    if isinstance(levels, torch.Tensor):
+        levels = levels.detach().cpu().numpy()
+    lv = np.asarray(levels, dtype=np.float32)
+    if lv.ndim > 1:
+        raise ValueError("levels must be a scalar or 1-D")
+    lv = np.ascontiguousarray(lv.reshape(-1))
+    if not bool(np.all((lv > 0) & (lv < 1))):
+        raise ValueError("quantile levels must lie strictly inside (0, 1) as float32 values")
+    if lv.size > MAX_LEVELS:
+        raise ValueError(f"at most {MAX_LEVELS} levels per call")
+    return lv
+
+
+def mixture_quantiles(mu_f, var_f, lik_var, weights, levels, out=None):
+    """Quantiles [N, Q] of the mixture predictive (mgp_mixture_quantiles): the y with
+    cdf(y) = p for a level p <= 1/2 and with sf(y) = 1 - p above, by a bracketed Newton
+    iteration per (point, level).  levels: host values in (0, 1) (checked here), rounded to
+    float32 once.  out: a float32 [N, Q] view with a contiguous last dimension."""
+    _latents_check(mu_f, var_f, "f")
+    K, N = mu_f.shape
+    _check(lik_var, "lik_var"), _check(weights, "weights", 2)
+    if tuple(weights.shape) != (N, K):
+        raise ValueError("weights must be [N, K]")
+    weights = weights.contiguous()
+    lv = quantile_levels(levels)
+    Q = lv.size
+    if out is None:
+        out = torch.empty(N, Q, dtype=F32, device=mu_f.device)
+    else:
+        _check(out, "out", 2)
+        if tuple(out.shape) != (N, Q):
+            raise ValueError("out must be [N, Q]")
+    if Q == 0:
+        return out
+    ldq = _ld(out) if N > 1 else Q
+    lvd = torch.from_numpy(lv).to(mu_f.device)
+    _lib.call("mgp_mixture_quantiles", mu_f.data_ptr(), var_f.data_ptr(), _ld(mu_f), lik_var.data_ptr(),
+              weights.data_ptr(), N, K, lvd.data_ptr(), Q, out.data_ptr(), ldq, _stream())
     return out
 
 
