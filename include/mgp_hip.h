@@ -29,8 +29,8 @@
  *    written; each entry's comment repeats its own):
  *      input dimension D <= 32: mgp_rbf_kuf, mgp_rbf_kuu (mgp_rbf_kuu_jitter),
  *        mgp_rbf_kuf_x6 / _f16, the Kuf side job of mgp_kuu_potrf_trtri_kuf,
- *        mgp_rbf_backward / _batch, mgp_full_cov_conditional, mgp_vq, mgp_kmeans_* (these
- *        also N <= 2^31 - 1, k <= N and R <= 64 runs);
+ *        mgp_rbf_backward / _batch, mgp_full_cov_conditional, mgp_path_eval, mgp_vq, mgp_kmeans_*
+ *        (these also N <= 2^31 - 1, k <= N and R <= 64 runs);
  *      D unbounded: mgp_kuu_potrf_trtri / _ev / _ex (a generic Kuu build above D = 32);
  *      experts K <= 16: K4 (mgp_trsm_stats, _x6, _x6_f16, _f16, _f16x8, _f16_batch) and the
  *        conditional backward (mgp_conditional_backward_*, its _prep_f16c);
@@ -925,6 +925,27 @@ int mgp_natgrad_step(float* q_mu, int64_t ldq, float* q_sqrt, int64_t ldqs, int6
                      int32_t grad_is_double, int64_t M, int32_t K, float step, float grad_sign, int32_t* info,
                      void* workspace, size_t workspace_bytes, mgp_stream_t stream);
 
+/* Evaluation of C frozen pathwise posterior samples at N points (csrc/paths.hip; Matheron's
+ * rule with a random-Fourier-feature prior, no counterpart in the reference):
+ *   out[c][n] = sum_{j < R} W[j][c] cos(2 pi (Omega_j . x_n + phase_j))
+ *             + sum_{m < M} W[R + m][c] A[m][n]
+ * X [N][ldx >= D]; Omega [R][ldo >= D] and phase [R] in turns (radians / 2 pi: the setup
+ * folds 1 / 2 pi into Omega = zeta / lengthscale); A [M][lda] = L^-1 Kuf as K4 writes it in f32
+ * (lda % 4 == 0, 16-B aligned; M == 0: prior features only, A is not read and may be NULL);
+ * W [R + M][ldw] (ldw % 4 == 0, 16-B aligned), its first R rows already scaled by
+ * sqrt(2 variance / R); out [C][ldout >= N], for C = S K columns c = s K + k the project's
+ * [S][K][N] latents.  Exact-f32 MFMA, the cosine rows generated on the fly (no [R][N] buffer,
+ * no workspace); fixed k order, no atomics: two calls give the same bits, and out[c][n] does
+ * not depend on N or on n's position, so a call on X[a:b] returns columns a .. b of the full
+ * call.  D <= 32 (D > 32: MGP_ERR_UNSUPPORTED); any R >= 1, M >= 0, C >= 1, N.
+ * -1 X, -2 ldx < D, -4 D < 1, -5 Omega, -6 ldo < D, -7 phase, -8 R < 1, -9 A (M > 0),
+ * -10 lda < N (M > 0), -11 M < 0, -12 W, -13 ldw < C, -14 C < 1, -15 out, -16 ldout < N;
+ * MGP_ERR_ALIGN for W or A; all checked before any pointer is read or HIP call made.
+ * N <= 0: MGP_OK after the checks, nothing done. */
+int mgp_path_eval(const float* X, int64_t ldx, int64_t N, int32_t D, const float* Omega, int64_t ldo,
+                  const float* phase, int64_t R, const float* A, int64_t lda, int64_t M, const float* W,
+                  int64_t ldw, int32_t C, float* out, int64_t ldout, mgp_stream_t stream);
+
 
 /* ---------------------------------------------------------------- the §8(b) front
  * One entry per reference operation in the default formats: what a
@@ -947,7 +968,8 @@ enum {
   MGP_OP_RBF_BACKWARD = 11,
   MGP_OP_FULL_COV_CONDITIONAL = 12,
   MGP_OP_MIXTURE_PREDICT = 13,
-  MGP_OP_MIXTURE_SCORE = 14
+  MGP_OP_MIXTURE_SCORE = 14,
+  MGP_OP_PATH_EVAL = 15   /* needs no workspace: 0 */
 };
 size_t mgp_workspace_bytes(int32_t op, int64_t M, int64_t N, int32_t K);
 /* Kuu = K(Z, Z) + jitter I in float32 (covariances.Kuu, models.py:135); same as

@@ -242,6 +242,9 @@ SIGNATURES = {
     "mgp_natgrad_step": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64,
                                         c_i32, c_i64, c_i32, ctypes.c_float, ctypes.c_float, c_ptr, c_ptr, c_size,
                                         c_ptr]),
+    # pathwise posterior samples (csrc/paths.hip)
+    "mgp_path_eval": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64,
+                                     c_ptr, c_i64, c_i32, c_ptr, c_i64, c_ptr]),
     # scipy.cluster.vq on the device (csrc/kmeans.hip)
     "mgp_vq": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_ptr]),
     "mgp_kmeans_workspace_bytes": (c_size, [c_i64, c_i64, c_i32, c_i32]),

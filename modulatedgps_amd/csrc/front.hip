@@ -127,6 +127,8 @@ extern "C" size_t mgp_workspace_bytes(int32_t op, int64_t M, int64_t N, int32_t 
       return mgp_mixture_predict_workspace_bytes(N, K);
     case MGP_OP_MIXTURE_SCORE:
       return mgp_mixture_score_workspace_bytes(N, K);
+    case MGP_OP_PATH_EVAL:
+      return 0;
     default:
       return 0;
   }

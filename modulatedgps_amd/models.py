@@ -450,6 +450,19 @@ class SVGPModified:
             samples = mean.unsqueeze(-3) + Lz.permute(*range(len(lead)), -1, -2, -3)
         return samples if num_samples is not None else samples.squeeze(-3)
 
+    # ------------------------------------------------------------------ pathwise samples
+    def sample_paths(self, num_samples, num_features=1024, seed=None, basis=None, noise=None):
+        """num_samples joint samples of the K latent functions as functions (paths.LayerPaths;
+        pathwise conditioning on num_features random Fourier features): the returned object
+        is a snapshot of the layer, paths(X) -> [S, N, K] for any X [N, D] at a cost linear in
+        N, and the same seed gives the same functions on every rank.  basis = (zeta [R, D],
+        phase [R] in turns) and noise = (w [S, K, R], eps [S, K, M]) are explicit draws; else
+        Philox draws keyed by `seed`, or by a fresh key of the layer.  1024 features is a
+        convention, not a measured optimum.  ValueError on bad arguments before anything is
+        uploaded."""
+        from .paths import LayerPaths
+        return LayerPaths(self, num_samples, num_features, seed=seed, basis=basis, noise=noise)
+
 
 class PrecomputeCacheType:
     """gpflow.posteriors.PrecomputeCacheType (TENSOR / VARIABLE / NOCACHE)."""
@@ -1417,6 +1430,16 @@ class SMGP(SGP):
                              process_group=process_group)
         self.check_linalg()
         return float(v.cpu())
+
+    def sample_paths(self, num_samples, num_features=1024, seed=None):
+        """Coherent function samples of the trained mixture (paths.MixturePaths): `.pred` and
+        `.assign` are SVGPModified.sample_paths of the two layers, and predict_f(X),
+        predict_logits(X), predict_weights(X) = softmax_k of the logit curves [S, N, K] and
+        predict_mean(X) = sum_k weights f [S, N] evaluate them at any X.  The relaxed-one-hot
+        sampling of W at tau = 1e-2 is left out: it is discontinuous in the logits.  A
+        MultiClass pred likelihood raises NotImplementedError from predict_mean."""
+        from .paths import MixturePaths
+        return MixturePaths(self, num_samples, num_features, seed=seed)
 
 
 class SMGPModified(SMGP):

@@ -1464,3 +1464,42 @@ def kmeans_update(obs, code, k, workspace=None):
     _lib.call("mgp_kmeans_update", obs.data_ptr(), ldo, N, D, code.data_ptr(), k, means.data_ptr(), D,
               counts.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream())
     return means, counts
+
+
+# --------------------------------------------------------------------------- pathwise samples
+def path_eval(X, Omega, phase, W, A=None, out=None):
+    """C frozen pathwise posterior samples at the N points of X (mgp_path_eval):
+        out[c, n] = sum_{j < R} W[j, c] cos(2 pi (Omega[j] . X[n] + phase[j])) + sum_m W[R + m, c] A[m, n]
+    X [N, D]; Omega [R, D] and phase [R] in turns (zeta / lengthscale / 2 pi); W [R + M, C]
+    with the prior rows scaled by sqrt(2 variance / R); A [M, N] = L^-1 Kuf in f32 as K4
+    writes it (None: the prior features only, W [R, C]).  Returns out [C, N], a view of
+    padded storage.  A call on X[a:b] returns out[:, a:b] of the full call bit for bit."""
+    X, ldx = _rows(X, "X")
+    Omega, ldo = _rows(Omega, "Omega")
+    _check(phase, "phase", 1), _check(W, "W", 2)
+    N, D = X.shape
+    R = Omega.shape[0]
+    if Omega.shape[1] != D:
+        raise ValueError(f"Omega must have X's {D} columns, got {tuple(Omega.shape)}")
+    if phase.numel() != R:
+        raise ValueError(f"phase must be [{R}], got {tuple(phase.shape)}")
+    M = 0
+    if A is not None:
+        _check(A, "A", 2)
+        M = A.shape[0]
+        if A.shape[1] != N:
+            raise ValueError(f"A must be [M, {N}], got {tuple(A.shape)}")
+        A = as_padded(A)
+    if W.shape[0] != R + M:
+        raise ValueError(f"W must have R + M = {R + M} rows, got {tuple(W.shape)}")
+    C = W.shape[1]
+    W = as_padded(W)
+    phase = phase.contiguous()
+    if out is None:
+        out = padded(C, N, X.device)
+    elif tuple(out.shape) != (C, N):
+        raise ValueError(f"out must be [{C}, {N}]")
+    _lib.call("mgp_path_eval", X.data_ptr(), ldx, N, D, Omega.data_ptr(), ldo, phase.data_ptr(), R,
+              A.data_ptr() if A is not None else None, _ld(A) if A is not None else 0, M, W.data_ptr(), _ld(W), C,
+              out.data_ptr(), _ld(out), _stream())
+    return out
