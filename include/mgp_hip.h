@@ -30,7 +30,8 @@
  *      input dimension D <= 32: mgp_rbf_kuf, mgp_rbf_kuu (mgp_rbf_kuu_jitter),
  *        mgp_rbf_kuf_x6 / _f16, the Kuf side job of mgp_kuu_potrf_trtri_kuf,
  *        mgp_rbf_backward / _batch, mgp_full_cov_conditional, mgp_path_eval, mgp_vq, mgp_kmeans_*
- *        (these also N <= 2^31 - 1, k <= N and R <= 64 runs);
+ *        (these also N <= 2^31 - 1, k <= N and R <= 64 runs), mgp_greedy_* (also N <= 2^31 - 1
+ *        and M <= N);
  *      D unbounded: mgp_kuu_potrf_trtri / _ev / _ex (a generic Kuu build above D = 32);
  *      experts K <= 16: K4 (mgp_trsm_stats, _x6, _x6_f16, _f16, _f16x8, _f16_batch) and the
  *        conditional backward (mgp_conditional_backward_*, its _prep_f16c);
@@ -61,7 +62,8 @@ enum {
   MGP_ERR_WORKSPACE = 1,   /* workspace pointer NULL or too small */
   MGP_ERR_ALIGN = 2,       /* leading dimension / pointer alignment */
   MGP_ERR_UNSUPPORTED = 3, /* size outside the supported range: D > 32, K > 16 (K4, conditional
-                              backward) or K > 32, a k-means size -- see "Size limits" above */
+                              backward) or K > 32, a k-means or greedy-selection size -- see "Size
+                              limits" above */
   MGP_ERR_HIP_BASE = 1000
 };
 
@@ -863,6 +865,47 @@ int mgp_kmeans_select(int64_t N, int64_t k, int32_t D, int32_t R, const void* wo
 int mgp_kmeans_update(const float* obs, int64_t ldo, int64_t N, int32_t D, const int32_t* code, int64_t k,
                       float* means, int64_t ldm, int32_t* counts, void* workspace, size_t workspace_bytes,
                       mgp_stream_t stream);
+
+/* ---------------------------------------------------------------- greedy variance selection (csrc/greedy.hip)
+ * Inducing points by greedy conditional variance (Burt, Rasmussen, van der Wilk 2020): the
+ * pivoted Cholesky of Kff = K(X, X) of the SquaredExponential kernel of mgp_rbf_kuf (n_ls = 1
+ * or D, hyper-parameters DEVICE pointers).  With d[n] = variance,
+ *   step i:  j = argmax_n d[n], ties to the lowest n;  stop if d[j] <= rel_threshold * variance
+ *            L[i][n] = (k(x_n, x_j) - sum_{t < i} L[t][n] L[t][j]) / sqrt(d[j])
+ *            d[n] = max(d[n] - L[i][n]^2, 0);  dmax[i] = d[j] before,  trace[i] = sum_n d[n] after.
+ * k(x_n, x_j), the dot product, d, dmax and trace are float64 (the differences of the float32
+ * inputs, the scaled squared distance and the exponential included); the factor L [M][ldl >= N]
+ * is stored float32, step-major (ldl % 4 == 0, 16-B aligned: MGP_ERR_ALIGN), and d is updated
+ * with the stored value.  Every sum runs in an order that depends on N and i alone and there
+ * are no floating-point atomics, so two calls, any B and any ldx, ldl return the same bits.
+ * X [N][ldx >= D] float32 (no alignment requirement).  One launch per step plus one per
+ * mgp_greedy_steps call; nothing waits across workgroups inside a launch.
+ * Limits, MGP_ERR_UNSUPPORTED one past them before anything is launched or written:
+ * D <= 32, N <= 2^31 - 1, 1 <= M <= N.  N == 0: MGP_OK after the argument checks, nothing done.
+ *
+ * The workspace of a selection of up to M of N points; 0 outside the limits.  It holds d, the
+ * pivots and the per-workgroup partials between the calls below and must be 16-B aligned. */
+size_t mgp_greedy_workspace_bytes(int64_t N, int64_t M, int32_t D);
+/* Start a selection: d[n] = variance, no point chosen.  -4: rel_threshold negative or NaN.
+ * The workspace may be sized for any M. */
+int mgp_greedy_init(int64_t N, int32_t D, const float* variance, double rel_threshold, void* workspace,
+                    size_t workspace_bytes, mgp_stream_t stream);
+/* The next min(B, M) steps.  Once a step meets the threshold it and every later one return at
+ * once, and no step runs beyond M, so the result does not depend on B.  state: DEVICE int32
+ * [2] = points chosen so far, stopped by the threshold (0 / 1), written at the end of the call
+ * -- the only thing a host that enqueues blocks of steps reads back; one that enqueues all M
+ * reads nothing.  X, M, the kernel, L and the workspace are the same in every call of a
+ * selection.  -7: n_ls is neither 1 nor D; -9: B < 1; -11: ldl < N. */
+int mgp_greedy_steps(const float* X, int64_t ldx, int64_t N, int32_t D, const float* variance,
+                     const float* lengthscales, int32_t n_ls, int64_t M, int32_t B, float* L, int64_t ldl,
+                     void* workspace, size_t workspace_bytes, int32_t* state, mgp_stream_t stream);
+/* The selection so far, m = info[0] points: indices (int64 [M]), Z [M][ldz >= D] = X[indices],
+ * dmax and trace (float64 [M]) -- the first m entries of each are written; residual (float64
+ * [N], may be NULL) = d, the diagonal of Kff - Qff, whose sum is trace[m - 1]; info (int32
+ * [2]) = m, stopped by the threshold. */
+int mgp_greedy_result(const float* X, int64_t ldx, int64_t N, int32_t D, int64_t M, const void* workspace,
+                      size_t workspace_bytes, int64_t* indices, float* Z, int64_t ldz, double* dmax,
+                      double* trace, double* residual, int32_t* info, mgp_stream_t stream);
 
 /* ---------------------------------------------------------------- optimizer
  * KL gradient folded into the ELBO gradient: g_q_mu -= q_mu / num_data,

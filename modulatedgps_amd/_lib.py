@@ -256,6 +256,13 @@ SIGNATURES = {
                                          c_ptr]),
     "mgp_kmeans_update": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr,
                                          c_size, c_ptr]),
+    # greedy conditional-variance selection of inducing points (csrc/greedy.hip)
+    "mgp_greedy_workspace_bytes": (c_size, [c_i64, c_i64, c_i32]),
+    "mgp_greedy_init": (ctypes.c_int, [c_i64, c_i32, c_ptr, ctypes.c_double, c_ptr, c_size, c_ptr]),
+    "mgp_greedy_steps": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_i32, c_i64, c_i32, c_ptr, c_i64,
+                                        c_ptr, c_size, c_ptr, c_ptr]),
+    "mgp_greedy_result": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_i64, c_ptr, c_size, c_ptr, c_ptr, c_i64,
+                                         c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
 }
 
 _lib = None

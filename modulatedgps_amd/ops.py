@@ -1466,6 +1466,60 @@ def kmeans_update(obs, code, k, workspace=None):
     return means, counts
 
 
+# --------------------------------------------------------------------------- greedy variance selection
+def greedy_workspace(N, M, D, device):
+    nbytes = _lib.load().mgp_greedy_workspace_bytes(N, M, D)
+    if nbytes == 0:
+        _lib.check("mgp_greedy_workspace_bytes", 3)
+    return _ws(nbytes, device)
+
+
+def greedy_factor(N, M, device):
+    """The float32 factor storage [M, N] of a selection, rows padded to a multiple of 4."""
+    return padded(M, N, device)
+
+
+def greedy_init(N, D, variance, threshold, workspace):
+    """Start a selection on N points (mgp_greedy_init): d = variance, nothing chosen."""
+    _check(variance, "variance")
+    _lib.call("mgp_greedy_init", N, D, variance.data_ptr(), float(threshold), workspace.data_ptr(),
+              workspace.numel(), _stream())
+
+
+def greedy_steps(X, variance, lengthscales, M, B, factor, workspace, state):
+    """The next min(B, M) steps of the selection (mgp_greedy_steps); factor: float32 [M, N]
+    view of greedy_factor; state: device int32 [2] = points chosen so far, stopped."""
+    X, ldx = _rows(X, "X")
+    _check(variance, "variance"), _check(lengthscales, "lengthscales"), _check(factor, "factor", 2)
+    N, D = X.shape
+    if factor.shape != (M, N):
+        raise ValueError(f"factor must be [M, N] = [{M}, {N}], got {tuple(factor.shape)}")
+    if state.dtype != I32 or not state.is_cuda or state.numel() < 2:
+        raise ValueError("state must be a device int32 tensor [2]")
+    _lib.call("mgp_greedy_steps", X.data_ptr(), ldx, N, D, variance.data_ptr(), lengthscales.data_ptr(),
+              lengthscales.numel(), M, int(B), factor.data_ptr(), _ld(factor),
+              workspace.data_ptr(), workspace.numel(), state.data_ptr(), _stream())
+
+
+def greedy_result(X, M, workspace, residual=True):
+    """The selection so far (mgp_greedy_result) -> (indices int64 [M], Z float32 [M, D], dmax
+    and trace float64 [M], residual float64 [N] or None, info int32 [2] = m, stopped); the
+    first m entries of the [M] arrays are written."""
+    X, ldx = _rows(X, "X")
+    N, D = X.shape
+    dev = X.device
+    indices = torch.empty(M, dtype=torch.int64, device=dev)
+    Z = torch.empty(M, D, dtype=F32, device=dev)
+    dmax = torch.empty(M, dtype=torch.float64, device=dev)
+    trace = torch.empty(M, dtype=torch.float64, device=dev)
+    res = torch.empty(N, dtype=torch.float64, device=dev) if residual else None
+    info = torch.empty(2, dtype=I32, device=dev)
+    _lib.call("mgp_greedy_result", X.data_ptr(), ldx, N, D, M, workspace.data_ptr(), workspace.numel(),
+              indices.data_ptr(), Z.data_ptr(), D, dmax.data_ptr(), trace.data_ptr(),
+              res.data_ptr() if residual else None, info.data_ptr(), _stream())
+    return indices, Z, dmax, trace, res, info
+
+
 # --------------------------------------------------------------------------- pathwise samples
 def path_eval(X, Omega, phase, W, A=None, out=None):
     """C frozen pathwise posterior samples at the N points of X (mgp_path_eval):
