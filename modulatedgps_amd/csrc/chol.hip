@@ -1465,8 +1465,6 @@ struct KufSideJob {
   void* const* Kfr; bool f16;
 };
 
-extern "C" size_t mgp_x6_cols_bytes(int64_t M, int64_t N);
-
 // Share of the image blocks per step launch j: proportional to the CUs the launch's tile
 // workgroups leave idle (one workgroup per CU: the step kernel's LDS), at least an eighth
 // of the CUs each.
@@ -1524,13 +1522,12 @@ static int chol_run(CholArgs& a, int batch, void* workspace, size_t workspace_by
   std::vector<int> knwg;
   if (kj && kj->N > 0 && a.M > 0) {
     a.kx = kj->X; a.kldx = kj->ldx; a.kN = kj->N; a.kf16 = kj->f16 ? 1 : 0;
-    const int64_t mp = (a.M + 127) / 128 * 128;
-    a.knmk = (int)(mp / 16);
+    a.knmk = kuf_nmk(a.M);
     a.krow_blocks = kuf_row_blocks(a.M);
     a.kblocks = kuf_blocks(a.M, kj->N);
     for (int b = 0; b < batch; ++b) {
       a.kfr[b] = (bf16x8*)kj->Kfr[b];
-      a.kbound[b] = (float*)((char*)kj->Kfr[b] + mgp_x6_cols_bytes(a.M, kj->N) - 256);  // image trailer
+      a.kbound[b] = trailer(kj->Kfr[b], cols_planes(a.M, kj->N));  // image trailer
     }
     if (a.nb >= 2) kuf_side_split(a.nb, batch, batch * a.kblocks, kbeg, knwg, s);
   }

@@ -16,8 +16,6 @@
 
 namespace mgp {
 
-constexpr int kStatRows = 64;   // rows of one stats tile (mgp_stats_tiles)
-
 static inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 static inline int64_t round4(int64_t x) { return (x + 3) / 4 * 4; }
 
@@ -28,16 +26,16 @@ template <int KMAX>
 __global__ __launch_bounds__(256) void col_stats_kernel(const float* __restrict__ A, int64_t lda,
                                                         const float* __restrict__ q_mu, int64_t ldq, int64_t M,
                                                         int64_t N, int K, float* __restrict__ stats, int64_t lds) {
-  __shared__ float sq[kStatRows * KMAX];
-  const int64_t t = blockIdx.y, m0 = t * kStatRows;
-  for (int i = threadIdx.x; i < kStatRows * KMAX; i += 256) {
+  __shared__ float sq[kTgBM * KMAX];
+  const int64_t t = blockIdx.y, m0 = t * kTgBM;
+  for (int i = threadIdx.x; i < kTgBM * KMAX; i += 256) {
     const int r = i / KMAX, k = i % KMAX;
     sq[i] = (m0 + r < M && k < K) ? q_mu[(m0 + r) * ldq + k] : 0.f;
   }
   __syncthreads();
   const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
-  const int rows = (int)std::min<int64_t>(kStatRows, M - m0);
+  const int rows = (int)std::min<int64_t>(kTgBM, M - m0);
   float s0 = 0.f, s[KMAX];
 #pragma unroll
   for (int k = 0; k < KMAX; ++k) s[k] = 0.f;
@@ -57,7 +55,7 @@ __global__ __launch_bounds__(256) void col_stats_kernel(const float* __restrict_
 template <int KMAX>
 static int launch_col_stats(const float* A, int64_t lda, const float* q_mu, int64_t ldq, int64_t M, int64_t N, int K,
                             float* stats, int64_t lds, hipStream_t s) {
-  const dim3 grid((unsigned)((N + 255) / 256), (unsigned)((M + kStatRows - 1) / kStatRows));
+  const dim3 grid((unsigned)((N + 255) / 256), (unsigned)((M + kTgBM - 1) / kTgBM));
   hipLaunchKernelGGL(col_stats_kernel<KMAX>, grid, dim3(256), 0, s, A, lda, q_mu, ldq, M, N, K, stats, lds);
   return launch_status();
 }

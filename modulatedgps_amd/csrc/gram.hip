@@ -1047,9 +1047,9 @@ extern "C" int mgp_gram_f16(const float* X, int64_t ldx, int64_t sx, int64_t MI,
 
 // mgp_gram_f16 (unweighted) with per-row bounds xb[MI], yb[MJ] instead of two scalars
 // (gram_x6_kernel<., false, true, true>; the conditional backward's g_Lm gram).
-int gram_f16_rowscaled(const float* X, int64_t ldx, int64_t MI, const float* Y, int64_t ldy, int64_t MJ, int64_t N,
-                       float alpha, int32_t mode, float* out, int64_t ldo, const float* xb, const float* yb,
-                       void* workspace, size_t workspace_bytes, mgp_stream_t stream) {
+int mgp::gram_f16_rowscaled(const float* X, int64_t ldx, int64_t MI, const float* Y, int64_t ldy, int64_t MJ, int64_t N,
+                            float alpha, int32_t mode, float* out, int64_t ldo, const float* xb, const float* yb,
+                            void* workspace, size_t workspace_bytes, mgp_stream_t stream) {
   if (!xb || !yb) return MGP_ERR_UNSUPPORTED;
   return gram_x6_launch(X, ldx, 0, MI, Y, ldy, 0, MJ, nullptr, 0, N, 1, alpha, mode, out, ldo, MI * ldo, workspace,
                         workspace_bytes, stream, xb, yb, nullptr, true);

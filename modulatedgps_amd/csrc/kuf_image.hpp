@@ -25,7 +25,7 @@
 
 #include <type_traits>
 
-#include "mgp_common.hpp"
+#include "frag_image.hpp"
 
 namespace mgp {
 
@@ -177,8 +177,12 @@ __device__ __forceinline__ void kuf_image_block(const KufImageArgs& a, int64_t b
 }
 
 // The image geometry of a Kuf image (rbf.hip's launch, chol.hip's side job): row
-// blocks of 128 rows, column groups of 128 columns over the padded Np = 256 ceil(N / 256).
-inline int kuf_row_blocks(int64_t M) { return (int)((M + 127) / 128); }
-inline int64_t kuf_blocks(int64_t M, int64_t N) { return ((N + 255) / 256 * 256 / 128) * kuf_row_blocks(M); }
+// blocks of kKufRows rows, column groups of kKufCols columns over the padded Np = x6_np(N);
+// kuf_nmk: the image's k-steps (its fragment index stride per column block).
+constexpr int kKufRows = 128, kKufCols = 128;   // kuf_image_block: 4 row tiles of 32, 4 waves x 32 columns
+static_assert(kX6BM % kKufRows == 0 && kX6BN % kKufCols == 0, "Kuf blocks tile the padded image");
+inline int kuf_row_blocks(int64_t M) { return (int)(x6_mp(M) / kKufRows); }
+inline int64_t kuf_blocks(int64_t M, int64_t N) { return (x6_np(N) / kKufCols) * kuf_row_blocks(M); }
+inline int kuf_nmk(int64_t M) { return (int)(x6_mp(M) / 16); }
 
 }  // namespace mgp

@@ -21,6 +21,16 @@ inline int hip_status(hipError_t e) { return e == hipSuccess ? MGP_OK : MGP_ERR_
 inline int launch_status() { return hip_status(hipGetLastError()); }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// ------------------------------------------------------------------ stats tiles
+// Rows of one tile of the column statistics stats[t][1 + K][N] (sum A^2, A^T q_mu):
+// mgp_stats_tiles(M) = ceil(M / kTgBM) tiles.  Every producer and reader of a stats slot
+// follows it: trigemm.hip's K4 row tile and finalize, front.hip's col_stats_kernel (its LDS
+// and grid), and the x6 / f16 K4, which fills two tiles per 128-row item (kTgBM = 64 only).
+#ifndef MGP_TG_BM
+#define MGP_TG_BM 64
+#endif
+constexpr int kTgBM = MGP_TG_BM;
+
 // fmean[k][n] = sum over nTs stats tiles; fvar[k][n] = var - sum_t ||A||^2 part
 // + sum over nTp expert partials (trigemm.hip; shared by the f32 and split-bf16 K5).
 int mgp_launch_cond_finalize(const float* stats, int64_t lds, int nTs, const float* part, int64_t ldp, int nTp,
@@ -36,6 +46,11 @@ struct CondFinLayer {
 };
 int mgp_launch_cond_finalize2(const CondFinLayer& l0, const CondFinLayer& l1, int64_t lds, int nTs, int64_t ldp,
                               int nTp, int64_t N, int K, int64_t ldf, hipStream_t s);
+
+// mgp_gram_f16 (unweighted) with per-row bounds xb[MI], yb[MJ] (gram.hip; the conditional backward's g_Lm gram).
+int gram_f16_rowscaled(const float* X, int64_t ldx, int64_t MI, const float* Y, int64_t ldy, int64_t MJ, int64_t N,
+                       float alpha, int32_t mode, float* out, int64_t ldo, const float* xb, const float* yb,
+                       void* workspace, size_t workspace_bytes, mgp_stream_t stream);
 
 // K3 (chol.hip) on float64 input: info[b] and LinvT[b] = (chol(A_b)^-1)^T as mgp_potrf_trtri
 // gives them, A_b = Ad + b strideAd ([M][ldad] doubles, symmetric) read without a float32
@@ -106,7 +121,7 @@ __device__ __forceinline__ floatx16 mfma32x32x2(float a, float b, floatx16 c) {
 __device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 // ------------------------------------------------------------------ split-bf16 (x6) images
-// See split3.hip.  A fragment is 64 lanes x 8 bf16 per plane (1 KiB); lane
+// See frag_image.hpp.  A fragment is 64 lanes x 8 bf16 per plane (1 KiB); lane
 // (r = lane & 31, h = lane >> 5), element j <-> k-row kperm(h, j) of a 16-row
 // k-step, the order in which a 32x32 accumulator holds its rows.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -190,10 +205,12 @@ __device__ __forceinline__ int img_exp(float bound) {
 // With the image maximum in [2^13, 2^14) both land in e4m3's range (<= 2^8):
 // hi 2^-6 keeps 3 mantissa bits down to 2^-14 of the maximum, lo 2^6 likewise.
 // write_lo = false (X8 only): plane 1 (f16 lo) is left unwritten -- the image then
-// feeds only the f16x8 K5, which reads planes 0 and 2.
+// feeds only the f16x8 K5, which reads planes 0 and 2.  (By reference, so that the
+// flag is resolved in each caller after inlining: by value, a file whose callers all pass a
+// constant compiles them differently from a file that also holds a run-time caller.)
 template <bool X8 = false>
 __device__ __forceinline__ void store_split_f16(bf16x8* __restrict__ dst, const float (&v)[8], float scale,
-                                                bool write_lo = true) {
+                                                const bool& write_lo = true) {
   halfx8 h, l;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {

@@ -4,7 +4,7 @@
 //     maximum |L_k[i][c]| over the lower triangle they read (the split-f16 image's scale
 //     bound, absmax_kernel<1>'s result);
 //   - one fragment of the split-f16 image of L_k = tril(q_sqrt[k]) (split_tri_kernel,
-//     split3.hip).
+//     images.hip).
 // Reference: models.py:79 (prior_kl -> gauss_kl(q_mu, q_sqrt) whitened) and the q_sqrt
 // operand of base_conditional (models.py:141-143).
 #pragma once

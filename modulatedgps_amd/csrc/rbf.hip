@@ -82,7 +82,7 @@ __global__ __launch_bounds__(kRbfThreads) void rbf_kernel(
   }
 }
 
-// K1 writing Kuf's split-bf16 / split-f16 image (split3.hip layout) instead of f32
+// K1 writing Kuf's split-bf16 / split-f16 image (frag_image.hpp layout) instead of f32
 // Kuf: one block of kuf_image.hpp per 256-thread workgroup (the body, its layout and
 // numerics are documented there; the K3 step launches run the same blocks as their
 // Kuf side job, mgp_kuu_potrf_trtri_kuf).
@@ -419,8 +419,6 @@ extern "C" int mgp_rbf_kuu(const float* Z, int64_t ldz, int64_t M, int32_t D, co
                     (hipStream_t)stream);
 }
 
-extern "C" size_t mgp_x6_cols_bytes(int64_t M, int64_t N);
-
 static int rbf_kuf_image(const float* X, int64_t ldx, const float* Z, int64_t ldz, int64_t N, int64_t M, int32_t D,
                          const float* variance, const float* lengthscales, int32_t n_ls, void* Kfr,
                          size_t kfr_bytes, mgp_stream_t stream, bool f16) {
@@ -439,12 +437,11 @@ static int rbf_kuf_image(const float* X, int64_t ldx, const float* Z, int64_t ld
   if (N == 0 || M == 0) return MGP_OK;
   if (kfr_bytes < mgp_x6_cols_bytes(M, N)) return -12;
   if (!aligned16(Kfr)) return MGP_ERR_ALIGN;
-  const int64_t Mp = (M + 127) / 128 * 128, Np = (N + 255) / 256 * 256;
-  const int nmk = (int)(Mp / 16);
-  const int row_blocks = (int)(Mp / 128);
-  const dim3 grid((unsigned)(Np / 128 * row_blocks)), block(kRbfThreads);
+  const int nmk = kuf_nmk(M);
+  const int row_blocks = kuf_row_blocks(M);
+  const dim3 grid((unsigned)kuf_blocks(M, N)), block(kRbfThreads);
   hipStream_t s = (hipStream_t)stream;
-  float* bound = (float*)((char*)Kfr + mgp_x6_cols_bytes(M, N) - 256);  // image trailer (split3.hip)
+  float* bound = trailer(Kfr, cols_planes(M, N));  // image trailer (frag_image.hpp)
 #define MGP_RBF_X6_CASE(DM)                                                                            \
   if (D <= DM) {                                                                                       \
     if (f16)                                                                                           \

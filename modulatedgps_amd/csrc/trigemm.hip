@@ -418,12 +418,8 @@ __global__ __launch_bounds__(256) void cond_finalize2_kernel(CondFinLayer l0, Co
 
 using namespace mgp;
 
-// Tile choice shared by K4 and K5: row tile BM = kTgBM always (the stats tiling
-// depends on it: T = ceil(M / BM)); column tile 256 for large N, else 128.
-#ifndef MGP_TG_BM
-#define MGP_TG_BM 64
-#endif
-constexpr int kTgBM = MGP_TG_BM;
+// Tile choice shared by K4 and K5: row tile BM = kTgBM (mgp_common.hpp) always (the stats
+// tiling depends on it: T = ceil(M / BM)); column tile 256 for large N, else 128.
 static inline int tg_bn(int64_t N) { return N >= 256 * 64 ? 256 : 128; }
 
 extern "C" int mgp_stats_tiles(int64_t M) { return (int)((M + kTgBM - 1) / kTgBM); }

@@ -56,7 +56,7 @@ def dev_noise(z, u, device):
 
 
 def decode_cols_image(img, M, N):
-    """Split-bf16 column image (modulatedgps_amd/csrc/split3.hip layout
+    """Split-bf16 column image (modulatedgps_amd/csrc/frag_image.hpp layout
     [nb][mk][plane][lane][8]) -> float64 [M, N] = hi + mid + lo."""
     Mp, Np = -(-M // 128) * 128, -(-N // 256) * 256
     nb, nmk = Np // 32, Mp // 16
