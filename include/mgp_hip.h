@@ -194,7 +194,7 @@ int mgp_expert_conditional_f32(const float* A, int64_t lda, const float* q_sqrt,
  * The same K-expert conditional on the bf16 matrix cores at f32 accuracy:
  * every f32 operand is split exactly into three bf16 planes and each product
  * is formed from the six plane products of weight >= 2^-16 (f32-accumulated;
- * see csrc/split3.hip).  Operands are passed as "fragment images":
+ * see csrc/x6_mainloop.hpp).  Operands are passed as "fragment images":
  *   mgp_split_lower_x6: L_k = band_part(q_sqrt[k], -1, 0) -> Lfr
  *       (mgp_x6_lower_bytes(M, K) bytes; replaces the band_part at
  *       models.py:141-143 and is rebuilt whenever q_sqrt changes);

@@ -1,690 +1,35 @@
-// K5 on the bf16 matrix cores at f32 accuracy ("split-bf16 x6").
+// The conditional backward: reverse mode of K4 and K5 on the 16-bit matrix cores.
 //
-// Reference: the same contraction as trigemm.hip's K5 -- for every expert k,
-// fvar[k][n] += sum_m' (L_k^T A)[m'][n]^2 with L_k = band_part(q_sqrt[k], -1, 0)
-// (GPflow base_conditional, reached from MixtureGPs/models.py:141-143).
+// Reference: reverse mode of GPflow base_conditional's A = triangular_solve(Lm, Kmn),
+// fmean = A^T q_mu, fvar = Knn - sum_m A^2 + sum_m' (L_k^T A)^2 with
+// L_k = band_part(q_sqrt[k], -1, 0) (MixtureGPs/models.py:141-143).  For the cotangents
+// G_mu = dELBO/dfmean and Gv = dELBO/dfvar ([K][N] each), in the order of
+// conditional_backward's steps:
+//     gA       = q_mu G_mu - 2 A sum_k Gv_k + 2 sum_k (S_k A) diag(Gv_k),  S_k = L_k L_k^T
+//                (with the forward's C_k = L_k^T A images: 2 sum_k L_k (C_k diag(Gv_k)))
+//     g_Kuf    = L^-T gA = Linv^T gA
+//     g_q_sqrt[k] = 2 tril(P_k L_k),  P_k = A diag(Gv_k) A^T
+//     g_Lm     = -tril(g_Kuf A^T),  g_q_mu = A G_mu^T,  g_var = sum Gv
 //
-// Every f32 operand x is split exactly into three bf16 planes,
-//     x = hi + mid + lo (+ |x| 2^-25 at most),   hi = bf16(x), mid = bf16(x - hi),
-//     lo = bf16(x - hi - mid)
-// (each difference is exact in f32).  A product is formed from the six plane
-// products whose weight is >= 2^-16 of the leading one,
-//     a b ~ a_hi b_hi + a_hi b_mid + a_mid b_hi + a_hi b_lo + a_mid b_mid + a_lo b_hi,
-// so the per-product error is a few f32 ulps and the sum is accumulated in the
-// f32 MFMA accumulator -- the accuracy class of an f32 GEMM.  Six
-// v_mfma_f32_32x32x16_bf16 (32 cycles each for 32x32x16) replace eight
-// v_mfma_f32_32x32x2_f32 (64 cycles each for 32x32x2): 192 vs 512 cycles per
-// 32x32x16 block, 2.7x the f32 matrix rate on the same silicon.
+// Images (frag_image.hpp; the products and the main loops: x6_mainloop.hpp).  Read: Afr,
+// A's image from K4 (trsm_stats.hip), with the f32 A; the images of S_k or of L_k and of
+// Linv, built here through images.hip's launchers; with the C path the C_k images of the
+// training K5 (expert_cond.hip).  Written: gA as an image (x6, or split-f16 with one
+// exponent per (128-row tile, column)), A's row image for the P_k gram, and the f32
+// gradients.  The grams (P_k, g_q_sqrt, g_Lm, g_q_mu) are gram.hip's.
 //
-// Data layout: the fragment images of frag_image.hpp (built once per step by images.hip, K1 and K4).
-//
-// K5x6 kernel: one 256-thread workgroup per item (expert k, row tile t of 128
-// rows m', column tile of 256 n).  Wave w owns all 128 rows x 64 columns
-// (4 x 2 accumulators of 32x32).  Per k-step (16 rows of m): the workgroup
-// stages the 12 KiB of L fragments of its 4 row sub-tiles in LDS (double
-// buffered, one barrier per k-step); each wave loads its 6 A fragments (6 KiB)
-// straight from global into registers one k-step ahead; 48 MFMAs per wave.
-// The triangle is exploited at row-tile granularity (k-steps start at 128 t);
-// the zero blocks inside the diagonal tile come from Lfr's zero fill.
-#include <stdlib.h>
-
+// Work: the MFMA kernels take one 256-thread workgroup per item of 128 rows x 128 or 256
+// columns in col_major_item's order (grad_a_c*: per row-tile pair, as K4); the kernels
+// that only read A or fold partials are described where they stand.
 #include <algorithm>
-#include <type_traits>
 
 #include "mgp_common.hpp"
 #include "frag_image.hpp"
-
-#ifndef MGP_K4_STORE_NT
-#define MGP_K4_STORE_NT 1   // K4's A-image stores non-temporal (0: plain, for A/B builds)
-#endif
+#include "x6_mainloop.hpp"
 
 namespace mgp {
 
-// Debug builds only (-DMGP_DBG_STAMPS, tools/k4_stamps.py): K4 phase times per
-// workgroup on the 100 MHz reference clock (one time base for every CU).
-#ifdef MGP_DBG_STAMPS
-__device__ unsigned long long g_k4_stamps[4096 * 8];
-#define K4STAMP(i, k) do { if (threadIdx.x == 0 && (i) >= 0 && (i) < 4096) g_k4_stamps[(i) * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define K4STAMP(i, k) do {} while (0)
-#endif
-
-__device__ __forceinline__ bf16x8 ld_frag(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
-  return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-
-// Item b -> (row tile t heavy-first, column tile tn, expert k); the K experts of
-// a column tile are 8 block ids apart (one XCD) when nTn % 8 == 0.
-// TN_OUTER: per XCD, one column tile at a time with all its row tiles (heavy first)
-// and experts, so A's column slab is fetched about once instead of once per row tile
-// (the 32x32x16 C-writing K5 of round 2: 1.60 -> 1.51 ms; without the C writes the
-// row-tile-outer order was faster, 1.33 vs 1.36 ms).  The 16x16x32 kernels use the
-// row-tile-outer order for both (MGP_K5C_TN_OUTER).
-template <bool TN_OUTER = false>
-__device__ __forceinline__ void x6_item(int b, int nTn, int K, int& t, int& tn, int& k, int grid = -1) {
-  if (TN_OUTER && nTn % 8 == 0) {
-    const int nT = (grid < 0 ? (int)gridDim.x : grid) / (nTn * K);
-    const int x = b & 7, j = b >> 3;
-    const int per_g = nT * K;
-    t = (j % per_g) / K;
-    tn = (j / per_g) * 8 + x;
-    k = j % K;
-    return;
-  }
-#ifndef MGP_K5_GROUP
-#define MGP_K5_GROUP 4
-#endif
-  // MGP_K5_GROUP = G > 0 (the default, 4): per XCD, groups of G column tiles, row tiles in
-  // the middle (group outer, then t, then the group's tiles x experts), so that a group's A
-  // slabs are re-read per row tile from L2 / MALL instead of re-streamed from HBM: K5 pair
-  // 4.31 -> 3.71 GB fetched per launch, ELBO step 3.347-3.353 -> 3.322-3.332 ms, training
-  // 14.52-14.58 -> 14.49-14.51 ms (profiles/r06zc_*, r06zd_*; G = 2 slower, 8 between).
-  // Items are unchanged, so the results are bit-identical; at c4's per-rank N (one group per
-  // XCD) the order is the row-tile-outer one.
-  if (MGP_K5_GROUP > 0 && nTn % 8 == 0 && (nTn / 8) % MGP_K5_GROUP == 0) {
-    constexpr int G = MGP_K5_GROUP > 0 ? MGP_K5_GROUP : 1;
-    const int nT = (grid < 0 ? (int)gridDim.x : grid) / (nTn * K);
-    const int x = b & 7, j = b >> 3;
-    const int g = j / (nT * G * K);
-    t = (j / (G * K)) % nT;
-    const int i = (j / K) % G;
-    k = j % K;
-    tn = (g * G + i) * 8 + x;
-    return;
-  }
-  if (nTn % 8 == 0) {
-    const int x = b & 7, j = b >> 3;
-    const int per_t = (nTn / 8) * K;
-    t = j / per_t;
-    const int rem = j % per_t;
-    tn = (rem / K) * 8 + x;
-    k = rem % K;
-  } else {
-    const int per_t = nTn * K;
-    t = b / per_t;
-    tn = (b % per_t) / K;
-    k = b % K;
-  }
-}
-
-// Item b -> (row tile t, column tile tn) for the one-matrix products (K4,
-// gA, gKuf): the nT row tiles of a column tile are adjacent block ids on one
-// XCD (b % 8), heaviest first, so the column slab of the B image they all read
-// is served from that XCD's L2.
-__device__ __forceinline__ void col_major_item(int b, int nT, int nTn, int& t, int& tn) {
-  if (nTn % 8 == 0) {
-    const int x = b & 7, j = b >> 3;
-    t = nT - 1 - j % nT;
-    tn = (j / nT) * 8 + x;
-  } else {
-    t = nT - 1 - b % nT;
-    tn = b / nT;
-  }
-}
-
-// Main loop shared by K4 and K5: acc[i][c] (row sub-tile i = 0..3 of the
-// 128-row tile, column sub-tile c = 0..1 of this wave's 64 columns) +=
-// sum over k-steps mk in [mk_begin, mk_end) (even count) of T-image blocks
-// (4 t + i, mk) x B-image blocks (nb0 + c, mk).  T fragments are staged in LDS
-// (shared by the 4 waves), B fragments go global -> registers one k-step ahead.
-//   tbase: byte offset of T block (mb = 4 t, mk = 0) of this matrix
-//   sB0:   byte offset of B block (nb0, mk = 0)
-template <int V>
-using ic = std::integral_constant<int, V>;
-
-// DIAG_FIRST (K5, T lower: block (mb, mk) zero for 16 mk + 15 < 32 mb): the
-// first 8 k-steps meet the diagonal and only sub-tiles i <= p of k-step pair p
-// are non-zero.  Otherwise (K4, T upper: zero for 16 mk > 32 mb + 31) the last
-// 8 k-steps do, with sub-tiles i >= p of pair p.  Those MFMAs are skipped
-// (8% of the work), everything else is unchanged.
-// DIAG: 1 = diagonal first (lower T), 2 = diagonal last (upper T), 0 = full T.
-// NC: column sub-tiles (32 wide) per wave (B blocks nb0 .. nb0 + NC - 1).
-// NPL: planes used (3 = x6 products; 2, 1 = K5's reduced modes, mfma_planes):
-// only those planes are loaded and staged.
-// F16: the images are split-f16 (mfma_fmt), NPL must be 2.
-// X8 (with F16): image planes 0 (f16 hi) and 2 (e4m3 cross terms) are loaded;
-// per k-step pair, two f16 hi products and one e4m3 MFMA for both pairs of
-// cross terms (mfma_f8x): 2 + 2 f16-product-equivalents instead of 6.
-// HOIST: all T fragment reads of a k-step issued before its MFMAs (trsm_bwd: 457 ->
-// 438 us; K4 +2.5 %, K5 unchanged -- so only there).
-// BH: called as bh(b, mk) on k-step mk's B fragments right before their MFMAs
-// (trsm_bwd16_kernel's per-column rescale of the gA image); NoBHook: nothing.
-struct NoBHook {
-  template <class B>
-  __device__ __forceinline__ void operator()(B&, int) const {}
-};
-template <int DIAG, int NC = 2, int NPL = 3, bool F16 = false, bool X8 = false, bool HOIST = false,
-          typename BH = NoBHook>
-__device__ __forceinline__ void x6_mainloop(floatx16 (&acc)[4][NC], bf16x8 (*sL)[4 * 3 * 64],
-                                            __amdgpu_buffer_rsrc_t rT, uint32_t tbase,
-                                            __amdgpu_buffer_rsrc_t rB, uint32_t sB0, int mk_begin,
-                                            int mk_end, int nmk, bool init = true, BH bhook = BH{}) {
-  static_assert(!X8 || (F16 && NPL == 2), "X8 reads split-f16 images");
-  auto PL = [](int p) { return (X8 && p == 1) ? 2 : p; };  // LDS / register plane -> image plane
-  const int tid = threadIdx.x, lane = tid & 63;
-  const uint32_t vB = 16u * lane;
-  const uint32_t sBc = (uint32_t)nmk * 3u * kFragBytes;  // B block nb0 + c at sB0 + c sBc
-  // T stage: 256 NPL 16-B units per k-step, NPL per thread: unit e = tid + 256 s ->
-  //   row sub-tile i = e / (64 NPL), plane p = (e / 64) % NPL, lane e % 64
-  //   byte offset tbase + ((i * nmk + mk) * 192 + p * 64 + lane) * 16; LDS unit (3 i + p) * 64 + lane
-  uint32_t vT[NPL];
-  int dT[NPL];
-#pragma unroll
-  for (int s = 0; s < NPL; ++s) {
-    const int e = tid + 256 * s, i = e / (64 * NPL), p = (e / 64) % NPL;
-    vT[s] = (uint32_t)((i * nmk * 192 + PL(p) * 64 + (e & 63)) * 16);
-    dT[s] = (3 * i + p) * 64 + (e & 63);
-  }
-  if (init) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int c = 0; c < NC; ++c)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][c][e] = 0.f;
-  }
-
-  auto load_b = [&](bf16x8 (&b)[NC][3], int mk) {
-    const uint32_t o = (uint32_t)mk * 3u * kFragBytes;
-#pragma unroll
-    for (int p = 0; p < NPL; ++p)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) b[c][p] = ld_frag(rB, vB, sB0 + c * sBc + o + PL(p) * kFragBytes);
-  };
-  auto load_t = [&](u32x4v (&st)[NPL], int mk) {
-    const uint32_t o = tbase + (uint32_t)mk * 192u * 16u;
-#pragma unroll
-    for (int s = 0; s < NPL; ++s) st[s] = __builtin_amdgcn_raw_buffer_load_b128(rT, vT[s], o, 0);
-  };
-  auto store_t = [&](int buf, const u32x4v (&st)[NPL]) {
-#pragma unroll
-    for (int s = 0; s < NPL; ++s) reinterpret_cast<u32x4v*>(sL[buf])[dT[s]] = st[s];
-  };
-  auto compute = [&](int buf, const bf16x8 (&b)[NC][3], auto ilo, auto ihi) {
-    constexpr int ILO = decltype(ilo)::value, IHI = decltype(ihi)::value;
-    if constexpr (HOIST) {  // every T fragment read of the k-step before its first MFMA
-    bf16x8 a[4][3];
-#pragma unroll
-    for (int i = ILO; i < IHI; ++i)
-#pragma unroll
-      for (int p = 0; p < NPL; ++p) a[i][p] = sL[buf][(i * 3 + p) * 64 + lane];
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = ILO; i < IHI; ++i)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) acc[i][c] = mfma_fmt<NPL, F16>(a[i], b[c], acc[i][c]);
-    } else {
-#pragma unroll
-    for (int i = ILO; i < IHI; ++i) {
-      bf16x8 a[3];
-#pragma unroll
-      for (int p = 0; p < NPL; ++p) a[p] = sL[buf][(i * 3 + p) * 64 + lane];
-#pragma unroll
-      for (int c = 0; c < NC; ++c) acc[i][c] = mfma_fmt<NPL, F16>(a, b[c], acc[i][c]);
-    }
-    }
-  };
-
-  // X8: the first k-step of a pair keeps its cross-term fragments for the second
-  bf16x8 ax_s[4], bx_s[NC];
-  auto compute_x8 = [&](int buf, const bf16x8 (&b)[NC][3], auto ilo, auto ihi, auto second) {
-    constexpr int ILO = decltype(ilo)::value, IHI = decltype(ihi)::value;
-    constexpr bool SECOND = decltype(second)::value;
-#pragma unroll
-    for (int i = ILO; i < IHI; ++i) {
-      const bf16x8 a_hi = sL[buf][(i * 3) * 64 + lane], a_x = sL[buf][(i * 3 + 1) * 64 + lane];
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        if constexpr (SECOND) acc[i][c] = mfma_f8x(ax_s[i], a_x, bx_s[c], b[c][1], acc[i][c]);
-        acc[i][c] = mfma_f16(a_hi, b[c][0], acc[i][c]);
-      }
-      if constexpr (!SECOND) ax_s[i] = a_x;
-    }
-    if constexpr (!SECOND) {
-#pragma unroll
-      for (int c = 0; c < NC; ++c) bx_s[c] = b[c][1];
-    }
-  };
-
-  bf16x8 b0[NC][3], b1[NC][3];
-  u32x4v st[NPL];
-  load_t(st, mk_begin);
-  load_b(b0, mk_begin);
-  store_t(0, st);
-  __syncthreads();
-  // two k-steps per iteration: LDS buffers and fragment sets alternate
-  // one pair of k-steps (mk, mk + 1) on sub-tiles [ilo, ihi); sched_barrier(0)
-  // pins the prefetch loads ahead of the MFMA block
-  auto pair = [&](int mk, auto ilo, auto ihi) {
-    load_t(st, mk + 1);
-    load_b(b1, mk + 1);
-    __builtin_amdgcn_sched_barrier(0);
-    bhook(b0, mk);
-    if constexpr (X8)
-      compute_x8(0, b0, ilo, ihi, std::false_type{});
-    else
-      compute(0, b0, ilo, ihi);
-    __builtin_amdgcn_sched_barrier(0);
-    store_t(1, st);
-    __syncthreads();
-    const int m2 = mk + 2 < nmk ? mk + 2 : nmk - 1;  // after the last pair: harmless reload
-    load_t(st, m2);
-    load_b(b0, m2);
-    __builtin_amdgcn_sched_barrier(0);
-    bhook(b1, mk + 1);
-    if constexpr (X8)
-      compute_x8(1, b1, ilo, ihi, std::true_type{});
-    else
-      compute(1, b1, ilo, ihi);
-    __builtin_amdgcn_sched_barrier(0);
-    store_t(0, st);
-    __syncthreads();
-  };
-  if constexpr (DIAG == 1) {
-    pair(mk_begin, ic<0>{}, ic<1>{});
-    pair(mk_begin + 2, ic<0>{}, ic<2>{});
-    pair(mk_begin + 4, ic<0>{}, ic<3>{});
-    pair(mk_begin + 6, ic<0>{}, ic<4>{});
-#pragma nounroll
-    for (int mk = mk_begin + 8; mk < mk_end; mk += 2) pair(mk, ic<0>{}, ic<4>{});
-  } else if constexpr (DIAG == 0) {
-#pragma nounroll
-    for (int mk = mk_begin; mk < mk_end; mk += 2) pair(mk, ic<0>{}, ic<4>{});
-  } else {
-#pragma nounroll
-    for (int mk = mk_begin; mk < mk_end - 8; mk += 2) pair(mk, ic<0>{}, ic<4>{});
-    pair(mk_end - 8, ic<0>{}, ic<4>{});
-    pair(mk_end - 6, ic<1>{}, ic<4>{});
-    pair(mk_end - 4, ic<2>{}, ic<4>{});
-    pair(mk_end - 2, ic<3>{}, ic<4>{});
-  }
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t img_rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, (int)bytes, 0x00020000);
-}
-
-// ------------------------------------------------------------------ K5 (x6)
-// F16: split-f16 images (NPL = 2) scaled by 2^img_exp(*a_bound), 2^img_exp(*l_bound).
-// X8: their hi planes on f16 MFMA and cross terms on e4m3 MFMA (mfma_f8x).
-template <int NPL, bool F16 = false, bool X8 = false>
-__global__ __launch_bounds__(256, 2) void expert_cond_x6_kernel(const bf16x8* __restrict__ Afr,
-                                                                const bf16x8* __restrict__ Lfr,
-                                                                uint32_t afr_bytes, uint32_t lfr_bytes,
-                                                                int nmk, int nmb, int nTn, int K,
-                                                                int64_t N, float* __restrict__ part,
-                                                                int64_t ldp, const float* __restrict__ a_bound,
-                                                                const float* __restrict__ l_bound) {
-  __shared__ bf16x8 sL[2][4 * 3 * 64];  // 2 x 12 KiB: [row sub-tile][plane][lane]
-  int t, tn, k;
-  x6_item(blockIdx.x, nTn, K, t, tn, k);
-  const int nTp = nmb / 4;
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  floatx16 acc[4][2];
-  x6_mainloop<1, 2, NPL, F16, X8>(acc, sL, img_rsrc(Lfr, lfr_bytes), (uint32_t)(((int64_t)k * nmb + 4 * t) * nmk) * 3u * kFragBytes,
-              img_rsrc(Afr, afr_bytes), (uint32_t)((8 * tn + 2 * w) * nmk) * 3u * kFragBytes, 8 * t, nmk, nmk);
-
-  // sum over the 128 rows of C^2 per column: 4 sub-tiles x 16 registers, then the lane halves
-  const int64_t nbase = (int64_t)tn * kX6BN + 64 * w + (lane & 31);
-  float* dst = part + ((int64_t)k * nTp + t) * ldp;
-  float unscale = 1.f;
-  if constexpr (F16) unscale = ldexpf(1.f, -2 * (img_exp(*a_bound) + img_exp(*l_bound)));
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) s = fmaf(acc[i][c][e], acc[i][c][e], s);
-    s += __shfl_xor(s, 32, 64);
-    if constexpr (F16) s *= unscale;
-    const int64_t n = nbase + 32 * c;
-    if (lane < 32 && n < N) dst[n] = s;
-  }
-}
-
-// ------------------------------------------------------------------ K5 (split-f16) on 16x16x32 MFMAs
-// The same contraction, items and split-f16 images as expert_cond_x6_kernel<2, true>,
-// on v_mfma_f32_16x16x32_f16 (16 cycles per 16x16x32 block: the same cycles per flop
-// as 32x32x16; the chip can hold a different clock per shape under load,
-// MI355X_MICROARCH.md, DVFS give-back item 7).  No new image format: one k-step PAIR
-// (32 deep) of the existing fragments is one MFMA k-step; lane l (i = l % 16,
-// q = l / 16) takes the 16 bytes of fragment k-step 2 ks + q / 2 at lane position
-// 16 (row block % 2) + i + 32 (q % 2) -- its 8 elements are 8 of the 32 m of the pair,
-// the same 8 for the A operand (L_k^T, rows m') and the B operand (A, columns n), so
-// the contraction is unchanged.  Wave w: 128 rows x 64 columns = 8 x 4 blocks of
-// 16 x 16; per pair the L fragments of the item's 4 row sub-tiles (16 KiB) are staged
-// in LDS (double buffered, one barrier per pair), the wave's B fragments go global ->
-// registers one pair ahead; 96 MFMAs per wave and pair.
-typedef float floatx4v __attribute__((ext_vector_type(4)));
-typedef _Float16 halfx2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ floatx4v mfma16_f16(bf16x8 a, bf16x8 b, floatx4v c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(halfx8, a), __builtin_bit_cast(halfx8, b), c,
-                                                0, 0, 0);
-}
-__device__ __forceinline__ floatx4v mfma16_bf16(bf16x8 a, bf16x8 b, floatx4v c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-// one 16x16 block: the plane products of mfma_fmt (x6: six bf16, split-f16: three f16)
-template <int NPL, bool F16>
-__device__ __forceinline__ floatx4v mfma16_fmt(const bf16x8 (&a)[3], const bf16x8 (&b)[3], floatx4v acc) {
-  if constexpr (F16) {
-    acc = mfma16_f16(a[1], b[0], acc);
-    acc = mfma16_f16(a[0], b[1], acc);
-    return mfma16_f16(a[0], b[0], acc);
-  } else if constexpr (NPL == 3) {
-    acc = mfma16_bf16(a[2], b[0], acc);
-    acc = mfma16_bf16(a[1], b[1], acc);
-    acc = mfma16_bf16(a[0], b[2], acc);
-    acc = mfma16_bf16(a[1], b[0], acc);
-    acc = mfma16_bf16(a[0], b[1], acc);
-    return mfma16_bf16(a[0], b[0], acc);
-  } else if constexpr (NPL == 2) {
-    acc = mfma16_bf16(a[1], b[0], acc);
-    acc = mfma16_bf16(a[0], b[1], acc);
-    return mfma16_bf16(a[0], b[0], acc);
-  } else {
-    return mfma16_bf16(a[0], b[0], acc);
-  }
-}
-
-// Main loop of the 16x16x32 kernels: acc[ib][cb] (16-row block ib = 0..7 of the 128-row
-// item, 16-column block cb = 0..3 of this wave's 64 columns) += sum over k-step PAIRS
-// ks in [ks_begin, ks_end) (even count) of T-image rows x B-image columns.  T fragments
-// of the item's 4 row sub-tiles, both k-steps of a pair and NPL planes are staged in LDS
-// (double buffered, one barrier per pair); B fragments go global -> registers one pair
-// ahead.  DIAG = 1: T lower (K5): the first 4 pairs meet the diagonal, pair p has row
-// blocks ib <= 2 p + 1; DIAG = 2: T upper (K4): the last 4 pairs do, pair p of them has
-// ib >= 2 p; 0: full.  (The zero sub-blocks inside come from the images' zero fill.)
-//   tbase: byte offset of T fragment (mb = 4 t, mk = 0); sB0: of B fragment (nb0, mk = 0)
-template <int DIAG, int NPL, bool F16>
-__device__ __forceinline__ void x6_mainloop16(floatx4v (&acc)[8][4], bf16x8 (*sL)[4 * 2 * 3 * 64],
-                                              __amdgpu_buffer_rsrc_t rT, uint32_t tbase, __amdgpu_buffer_rsrc_t rB,
-                                              uint32_t sB0, int ks_begin, int ks_end, int nmk) {
-  const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, q = lane >> 4;
-  // T staging: unit e = tid + 256 s (NPL 2: 4 units, 3: 6 units per thread): sub-tile
-  // i = e / (128 NPL), k-step kk = (e / (64 NPL)) % 2, plane p = (e / 64) % NPL, position e % 64
-  constexpr int NU = 2 * NPL;
-  uint32_t vT[NU];
-#pragma unroll
-  for (int s = 0; s < NU; ++s) {
-    const int e = tid + 256 * s, i = e / (128 * NPL), kk = (e / (64 * NPL)) % 2, p = (e / 64) % NPL;
-    vT[s] = (uint32_t)((((i * nmk + kk) * 3 + p) * 64 + (e & 63)) * 16);
-  }
-  // B: column block cb, plane p, pair ks: fragment nb0 + cb / 2, k-step 2 ks + q / 2,
-  // position 16 (cb % 2) + li + 32 (q % 2)
-  const uint32_t vB = (uint32_t)((((q >> 1) * 3) * 64 + li + 32 * (q & 1)) * 16);
-  auto boff = [&](int cb, int p, int ks) {
-    return sB0 + (uint32_t)(cb >> 1) * (uint32_t)nmk * 3u * kFragBytes + (uint32_t)((2 * ks) * 3 + p) * kFragBytes +
-           (uint32_t)(16 * (cb & 1)) * 16u;
-  };
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[i][c] = floatx4v{0.f, 0.f, 0.f, 0.f};
-  auto load_b = [&](bf16x8 (&b)[4][3], int ks) {
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-      for (int p = 0; p < NPL; ++p) b[cb][p] = ld_frag(rB, vB, boff(cb, p, ks));
-  };
-  auto load_t = [&](u32x4v (&st)[NU], int ks) {
-    const uint32_t o = tbase + (uint32_t)(2 * ks) * 3u * kFragBytes;
-#pragma unroll
-    for (int s = 0; s < NU; ++s) st[s] = __builtin_amdgcn_raw_buffer_load_b128(rT, vT[s], o, 0);
-  };
-  auto store_t = [&](int buf, const u32x4v (&st)[NU]) {
-#pragma unroll
-    for (int s = 0; s < NU; ++s) reinterpret_cast<u32x4v*>(sL[buf])[tid + 256 * s] = st[s];
-  };
-  // A operand of row block ib, plane p: sub-tile ib / 2, k-step q / 2, position 16 (ib % 2) + li + 32 (q % 2)
-  const int aoff = (q >> 1) * 64 * NPL + li + 32 * (q & 1);
-  auto compute = [&](int buf, const bf16x8 (&b)[4][3], auto ilo, auto ihi) {
-    constexpr int ILO = decltype(ilo)::value, IHI = decltype(ihi)::value;
-#pragma unroll
-    for (int ib = ILO; ib < IHI; ++ib) {
-      const int base = (ib >> 1) * 128 * NPL + 16 * (ib & 1) + aoff;
-      bf16x8 a[3];
-#pragma unroll
-      for (int p = 0; p < NPL; ++p) a[p] = sL[buf][base + 64 * p];
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb) acc[ib][cb] = mfma16_fmt<NPL, F16>(a, b[cb], acc[ib][cb]);
-    }
-  };
-  bf16x8 b0[4][3], b1[4][3];
-  u32x4v st[NU];
-  load_t(st, ks_begin);
-  load_b(b0, ks_begin);
-  store_t(0, st);
-  __syncthreads();
-  auto two = [&](int ks, auto ilo0, auto ihi0, auto ilo1, auto ihi1) {
-    load_t(st, ks + 1);
-    load_b(b1, ks + 1);
-    __builtin_amdgcn_sched_barrier(0);
-    compute(0, b0, ilo0, ihi0);
-    __builtin_amdgcn_sched_barrier(0);
-    store_t(1, st);
-    __syncthreads();
-    const int k2 = ks + 2 < ks_end ? ks + 2 : ks_end - 1;  // after the last pair: harmless reload
-    load_t(st, k2);
-    load_b(b0, k2);
-    __builtin_amdgcn_sched_barrier(0);
-    compute(1, b1, ilo1, ihi1);
-    __builtin_amdgcn_sched_barrier(0);
-    store_t(0, st);
-    __syncthreads();
-  };
-  if constexpr (DIAG == 1) {
-    two(ks_begin, ic<0>{}, ic<2>{}, ic<0>{}, ic<4>{});
-    two(ks_begin + 2, ic<0>{}, ic<6>{}, ic<0>{}, ic<8>{});
-#pragma nounroll
-    for (int ks = ks_begin + 4; ks < ks_end; ks += 2) two(ks, ic<0>{}, ic<8>{}, ic<0>{}, ic<8>{});
-  } else if constexpr (DIAG == 0) {
-#pragma nounroll
-    for (int ks = ks_begin; ks < ks_end; ks += 2) two(ks, ic<0>{}, ic<8>{}, ic<0>{}, ic<8>{});
-  } else {
-#pragma nounroll
-    for (int ks = ks_begin; ks < ks_end - 4; ks += 2) two(ks, ic<0>{}, ic<8>{}, ic<0>{}, ic<8>{});
-    two(ks_end - 4, ic<0>{}, ic<8>{}, ic<2>{}, ic<8>{});
-    two(ks_end - 2, ic<4>{}, ic<8>{}, ic<6>{}, ic<8>{});
-  }
-}
-
-// ------------------------------------------------------------------ K5 (split-f16) on 16x16x32 MFMAs
-// The same contraction, items and split-f16 images as expert_cond_x6_kernel<2, true>,
-// on v_mfma_f32_16x16x32_f16 (16 cycles per 16x16x32 block: the same cycles per flop
-// as 32x32x16; the chip can hold a different clock per shape under load,
-// MI355X_MICROARCH.md, DVFS give-back item 7).  No new image format: one k-step PAIR
-// (32 deep) of the existing fragments is one MFMA k-step; lane l (i = l % 16,
-// q = l / 16) takes the 16 bytes of fragment k-step 2 ks + q / 2 at lane position
-// 16 (row block % 2) + i + 32 (q % 2) -- its 8 elements are 8 of the 32 m of the pair,
-// the same 8 for the A operand (L_k^T, rows m') and the B operand (A, columns n), so
-// the contraction is unchanged (x6_mainloop16).  Wave w: 128 rows x 64 columns =
-// 8 x 4 blocks of 16 x 16; 96 MFMAs per wave and pair.
-// COUT (training): C_k = L_k^T A is also written as a split-f16 B-layout image per expert,
-// (the B-layout of the images K4 writes); a fragment's lane position takes
-// 8 rows from two lanes of the 16x16 accumulator layout (one exchange across the lane halves).
-// One item (workgroup index b of a launch of `grid` items) of the split-f16 K5.
-// C_k images (training) with non-temporal stores (MGP_C_NT)
-#ifndef MGP_C_NT
-#define MGP_C_NT 1
-#endif
-constexpr bool kCntStores = MGP_C_NT;
-// C-writing K5 (training) in the column-tile-outer item order (x6_item TN_OUTER): measured
-// against the forward's row-tile-outer order on the 16x16x32 kernel, training step 14.18-14.22
-// vs 14.11-14.18 ms (profiles/r06o_train_ab.log) -- so the row-tile-outer order (0) is kept
-#ifndef MGP_K5C_TN_OUTER
-#define MGP_K5C_TN_OUTER 0
-#endif
-constexpr bool kK5cTnOuter = MGP_K5C_TN_OUTER;
-#ifndef MGP_K5_TN_OUTER
-#define MGP_K5_TN_OUTER 0   // the forward K5's item order (0: row tile outer)
-#endif
-constexpr bool kK5TnOuter = MGP_K5_TN_OUTER;
-template <bool COUT>
-__device__ __forceinline__ void expert_cond16_item(bf16x8 (*sL)[4 * 2 * 3 * 64], int b, int grid,
-                                                   const bf16x8* __restrict__ Afr, const bf16x8* __restrict__ Lfr,
-                                                   uint32_t afr_bytes, uint32_t lfr_bytes, int nmk, int nmb, int nTn,
-                                                   int K, int64_t N, float* __restrict__ part, int64_t ldp,
-                                                   const float* __restrict__ a_bound,
-                                                   const float* __restrict__ l_bound, bf16x8* __restrict__ Cfr,
-                                                   int64_t cexp, const float* __restrict__ colmax) {
-  int t, tn, k;
-  x6_item<COUT ? kK5cTnOuter : kK5TnOuter>(b, nTn, K, t, tn, k, grid);
-  const int nTp = nmb / 4;
-  const int lane = threadIdx.x & 63, li = lane & 15, q = lane >> 4;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  floatx4v acc[8][4];
-  x6_mainloop16<1, 2, true>(acc, sL, img_rsrc(Lfr, lfr_bytes), (uint32_t)(((int64_t)k * nmb + 4 * t) * nmk) * 3u * kFragBytes,
-                            img_rsrc(Afr, afr_bytes), (uint32_t)((8 * tn + 2 * w) * nmk) * 3u * kFragBytes, 4 * t,
-                            nmk / 2, nmk);
-  if constexpr (COUT) {
-    const float cmul = ldexpf(1.f, img_exp(*colmax * *a_bound * 1.0009765625f) -
-                                       (img_exp(*a_bound) + img_exp(*l_bound)));
-    bf16x8* Ck = Cfr + (int64_t)k * cexp;
-    const bool lo_half = lane < 32;
-    const int pos = lo_half ? li + 32 * q : 16 + li + 32 * (q - 2);
-#pragma unroll
-    for (int ib = 0; ib < 8; ++ib)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        float v[8];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {  // lanes 0-31: (own 2c, lane + 32's 2c); 32-63: (lane - 32's 2c + 1, own)
-          float x0 = acc[ib][2 * c][r], x1 = acc[ib][2 * c + 1][r];
-          lane_half_swap(x0, x1);
-          v[r] = x0 * cmul;
-          v[4 + r] = x1 * cmul;
-        }
-        bf16x8* dst = Ck + ((((int64_t)8 * tn + 2 * w + c) * nmk + 8 * t + ib) * 3) * 64 + pos;
-        if constexpr (kCntStores) {  // read back only by the backward, long after: past L2
-          halfx8 h, l;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const _Float16 hi = (_Float16)v[j];
-            h[j] = hi;
-            l[j] = (_Float16)(v[j] - (float)hi);
-          }
-          __builtin_nontemporal_store(__builtin_bit_cast(bf16x8, h), dst);
-          __builtin_nontemporal_store(__builtin_bit_cast(bf16x8, l), dst + 64);
-        } else {
-          store_split_f16(dst, v, 1.f);
-        }
-      }
-  }
-  // sum over the 128 rows of C^2 per column: 8 blocks x 4 registers, then the 4 lane groups
-  const float unscale = ldexpf(1.f, -2 * (img_exp(*a_bound) + img_exp(*l_bound)));
-  float* dst = part + ((int64_t)k * nTp + t) * ldp;
-#pragma unroll
-  for (int cb = 0; cb < 4; ++cb) {
-    float s = 0.f;
-#pragma unroll
-    for (int ib = 0; ib < 8; ++ib)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) s = fmaf(acc[ib][cb][r], acc[ib][cb][r], s);
-    s += lane_xor16(s);
-    s += lane_xor32(s);
-    const int64_t n = (int64_t)tn * kX6BN + 64 * w + 16 * cb + li;
-    if (lane < 16 && n < N) dst[n] = s * unscale;
-  }
-}
-
-template <bool COUT = false>
-__global__ __launch_bounds__(256, 2) void expert_cond16_kernel(const bf16x8* __restrict__ Afr,
-                                                               const bf16x8* __restrict__ Lfr, uint32_t afr_bytes,
-                                                               uint32_t lfr_bytes, int nmk, int nmb, int nTn, int K,
-                                                               int64_t N, float* __restrict__ part, int64_t ldp,
-                                                               const float* __restrict__ a_bound,
-                                                               const float* __restrict__ l_bound,
-                                                               bf16x8* __restrict__ Cfr = nullptr, int64_t cexp = 0,
-                                                               const float* __restrict__ colmax = nullptr) {
-  __shared__ bf16x8 sL[2][4 * 2 * 3 * 64];  // [row sub-tile][k-step of pair][plane][lane position] (2 planes used)
-  expert_cond16_item<COUT>(sL, blockIdx.x, gridDim.x, Afr, Lfr, afr_bytes, lfr_bytes, nmk, nmb, nTn, K, N, part, ldp,
-                           a_bound, l_bound, Cfr, cexp, colmax);
-}
-
-// One layer's operands of the batched K5.
-struct K5Layer {
-  const bf16x8* Afr;
-  const bf16x8* Lfr;
-  float* part;
-  const float* a_bound;
-  const float* l_bound;
-  bf16x8* Cfr;
-  const float* colmax;
-};
-
-// expert_cond16_kernel over two layers in one launch: workgroups [0, per) run layer 0's
-// items, [per, 2 per) layer 1's (same items, same arithmetic: bit-identical partials
-// and C_k images); one kernel tail fewer between the layers.
-template <bool COUT>
-__global__ __launch_bounds__(256, 2) void expert_cond16_pair_kernel(K5Layer l0, K5Layer l1, int per,
-                                                                    uint32_t afr_bytes, uint32_t lfr_bytes, int nmk,
-                                                                    int nmb, int nTn, int K, int64_t N, int64_t ldp,
-                                                                    int64_t cexp) {
-  __shared__ bf16x8 sL[2][4 * 2 * 3 * 64];
-  const bool second = (int)blockIdx.x >= per;
-  const K5Layer& l = second ? l1 : l0;
-  expert_cond16_item<COUT>(sL, (int)blockIdx.x - (second ? per : 0), per, l.Afr, l.Lfr, afr_bytes, lfr_bytes, nmk,
-                           nmb, nTn, K, N, l.part, ldp, l.a_bound, l.l_bound, l.Cfr, cexp, l.colmax);
-}
-
 // ------------------------------------------------------------------ backward (x6)
-// Store a 128 x 256 item's accumulators (wave w: 128 rows x 64 columns) as f32
-// rows [i0 + .][n0 + .] of out (M rows, leading dimension ld), each column n
-// scaled by colscale[n] (if given).  Buffer stores with 32-bit offsets: rows
-// beyond M fall outside the resource and are dropped.
-__device__ __forceinline__ void store_acc_f32(const floatx16 (&acc)[4][2], float* __restrict__ out, int64_t ld,
-                                              int64_t i0, int64_t n0, int64_t M, int64_t N,
-                                              const float* __restrict__ colscale) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const __amdgpu_buffer_rsrc_t r =
-      __builtin_amdgcn_make_buffer_rsrc((void*)out, (short)0, (int)(uint32_t)(M * ld * 4), 0x00020000);
-  const uint32_t soff = (uint32_t)((i0 * ld + n0) * 4);
-  const uint32_t ld32 = (uint32_t)ld;
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const int nl = 64 * w + 32 * c + (lane & 31);
-    const int64_t n = n0 + nl;
-    if (n < N) {
-      const float cs = colscale ? colscale[n] : 1.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const uint32_t rl = (uint32_t)(32 * i + acc_row(e, lane));
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, acc[i][c][e] * cs), r,
-                                                (rl * ld32 + (uint32_t)nl) * 4u, soff, 0);
-        }
-    }
-  }
-}
-
-// Store the accumulators as the split image [nb][mk] of the item's 128 x 256
-// block (as K4 does for A), columns scaled by colscale[n] (0 beyond N).
-__device__ __forceinline__ void store_acc_image(const floatx16 (&acc)[4][2], bf16x8* __restrict__ img, int nmk,
-                                                int t, int tn, int64_t N, const float* __restrict__ colscale) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const int64_t nb = 8 * (int64_t)tn + 2 * w + c;
-    const int64_t n = 32 * nb + (lane & 31);
-    const float cs = colscale ? (n < N ? colscale[n] : 0.f) : 1.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int64_t mk = 8 * (int64_t)t + 2 * i;
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = acc[i][c][8 * s + j] * cs;
-        store_split(img + ((nb * nmk + mk + s) * 3) * 64 + lane, v);
-      }
-    }
-  }
-}
-
 // gA0[m][n] = sum_k q_mu[m][k] G_mu[k][n] - 2 A[m][n] sum_k Gv[k][n]: the part
 // of the A gradient that needs no GEMM (one thread per column n, looping rows).
 template <int KMAX>
@@ -1832,895 +1177,9 @@ __global__ __launch_bounds__(1024) void rowmax_fold_kernel(const float* __restri
   }
 }
 
-// ------------------------------------------------------------------ K4 (x6)
-// A = LinvT^T Kuf from the images Tfr (LinvT, upper) and Kfr (Kuf): item =
-// (row tile t of 128 rows, heavy = large t first; column tile tn of 256), the
-// 16 k-steps... 8 t + 8 k-steps of the lower triangle.  Epilogue: the A image
-// (registers 8 s .. 8 s + 7 of each 32x32 tile are one B fragment of K5) and
-// the stats of the two 64-row stats tiles 2 t, 2 t + 1 (same layout as the
-// f32 K4: stats[st][0][n] = sum A^2, stats[st][1 + kk][n] = sum A q_mu[., kk]).
-// a_var != nullptr: A's image is split-f16, scaled by 2^img_exp(sqrt(*a_var))
-// (|A[m][n]| <= ||A[:, n]|| <= sqrt(k(x_n, x_n)) = sqrt(variance): the Nystrom
-// bound; the image trailer a_bound receives sqrt(*a_var) for the consumer).
-// F16IN: Tfr and Kfr are split-f16 images (scales 2^img_exp(*t_bound),
-// 2^img_exp(*k_bound)): three f16 products per block instead of six bf16 ones;
-// the accumulators are unscaled (exact power of two) before the epilogue.
-// X8OUT (with F16OUT): the A image also gets its e4m3 cross-term plane (K5 f16x8);
-// its f16 lo plane only when the f32 A is written too (training: the backward
-// reads planes 0-1), so a forward-only image moves 4 B per element, not 6.
-template <int KMAX, bool F16OUT = false, bool F16IN = false, bool X8OUT = false>
-__device__ __forceinline__ void trsm_stats_x6_item(
-    bf16x8 (*sL)[4 * 3 * 64], float* __restrict__ sQ, int t, int tn, const bf16x8* __restrict__ Tfr,
-    uint32_t tfr_bytes, const bf16x8* __restrict__ Kfr, uint32_t kfr_bytes, int nmk, int64_t M, int64_t N,
-    const float* __restrict__ q_mu, int64_t ldq, int K, bf16x8* __restrict__ Afr, float* __restrict__ stats,
-    int64_t lds_, float* __restrict__ Af32, int64_t lda, const float* __restrict__ a_var,
-    const float* __restrict__ t_bound = nullptr, const float* __restrict__ k_bound = nullptr) {
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t i0 = 128 * (int64_t)t;
-  float a_scale = 1.f;
-  if constexpr (F16OUT) a_scale = ldexpf(1.f, img_exp(sqrtf(*a_var)));
-  // q_mu rows of this row tile -> LDS [128][KMAX] before the main loop (whose
-  // barriers publish it), so the epilogue never waits on a global load.  F16OUT:
-  // also max |q_mu| of the tile (sQ[128 KMAX], as float bits; the caller zeroes
-  // it), the power-of-two scale of the split q_mu operand of the stats MFMAs
-  if (stats) {
-    float qmax = 0.f;
-    for (int idx = threadIdx.x; idx < 128 * KMAX; idx += 256) {
-      const int r = idx / KMAX, kk = idx % KMAX;
-      const float q = (i0 + r < M && kk < K) ? q_mu[(i0 + r) * ldq + kk] : 0.f;
-      sQ[idx] = q;
-      qmax = fmaxf(qmax, fabsf(q));
-    }
-    if constexpr (F16OUT) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) qmax = fmaxf(qmax, __shfl_xor(qmax, off, 64));
-      if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned int*>(sQ + 128 * KMAX), __float_as_uint(qmax));
-    }
-  }
-  floatx16 acc[4][2];
-  x6_mainloop<2, 2, F16IN ? 2 : 3, F16IN>(acc, sL, img_rsrc(Tfr, tfr_bytes), (uint32_t)(4 * t * nmk) * 3u * kFragBytes,
-                                          img_rsrc(Kfr, kfr_bytes),
-                                          (uint32_t)((8 * tn + 2 * w) * nmk) * 3u * kFragBytes, 0, 8 * t + 8, nmk);
-  if constexpr (F16IN) {
-    const float unscale = ldexpf(1.f, -(img_exp(*t_bound) + img_exp(*k_bound)));
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][c][e] *= unscale;
-  }
-  if (Af32) store_acc_f32(acc, Af32, lda, i0, (int64_t)tn * kX6BN, M, N, nullptr);
-  // ---- epilogue by 32-row sub-tile i: the A image fragments of acc[i] and its
-  // contribution to the stats of 64-row stats tile i / 2 (stats[st][0][n] = sum A^2,
-  // stats[st][1 + kk][n] = sum A q_mu[., kk]); acc[i] dies after its sub-tile, which
-  // keeps the live set to the remaining accumulators + 2 (1 + KMAX) sums (no spills)
-  if constexpr (F16OUT) {
-    // ---- split-f16: the A image, and the stats q_mu^T A on the matrix cores --
-    // per 16-row k-step, the image fragments of acc[i][c] (B operand, k = rows)
-    // times the split q_mu fragment (A operand: rows kk < K, k = the same 16
-    // rows, from sQ) into sq[c] (32 x 32, rows kk); sum A^2 stays VALU.  Stats
-    // tile st = 2 t + i / 2 (64 rows) as the VALU path.
-    const int qe = img_exp(__uint_as_float(reinterpret_cast<const unsigned int*>(sQ)[128 * KMAX]));
-    const float q_scale = ldexpf(1.f, qe), s_unscale = ldexpf(1.f, -(qe + img_exp(sqrtf(*a_var))));
-    const int r = lane & 31, h = lane >> 5;
-    floatx16 sq[2];
-    float a2[2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if ((i & 1) == 0) {
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          a2[c] = 0.f;
-#pragma unroll
-          for (int e = 0; e < 16; ++e) sq[c][e] = 0.f;
-        }
-      }
-      const int64_t mk = 8 * (int64_t)t + 2 * i;
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        bf16x8 qf[3];
-        if (stats) {
-          halfx8 qh, ql;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float x = (r < K ? sQ[(32 * i + 16 * s2 + kperm(h, j)) * KMAX + (r < KMAX ? r : 0)] : 0.f) * q_scale;
-            const _Float16 xh = (_Float16)x;
-            qh[j] = xh;
-            ql[j] = (_Float16)(x - (float)xh);
-          }
-          qf[0] = __builtin_bit_cast(bf16x8, qh);
-          qf[1] = __builtin_bit_cast(bf16x8, ql);
-        }
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const int64_t nb = 8 * (int64_t)tn + 2 * w + c;
-          float v[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = acc[i][c][8 * s2 + j];
-          store_split_f16<X8OUT>(Afr + ((nb * nmk + mk + s2) * 3) * 64 + lane, v, a_scale, Af32 != nullptr);
-          if (stats) {
-            halfx8 vh, vl;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              const float x = v[j] * a_scale;
-              const _Float16 xh = (_Float16)x;
-              vh[j] = xh;
-              vl[j] = (_Float16)(x - (float)xh);
-              a2[c] = fmaf(v[j], v[j], a2[c]);
-            }
-            const bf16x8 bf[3] = {__builtin_bit_cast(bf16x8, vh), __builtin_bit_cast(bf16x8, vl), bf16x8{}};
-            sq[c] = mfma_fmt<2, true>(qf, bf, sq[c]);
-          }
-        }
-      }
-      if (stats && (i & 1)) {
-        const int64_t st = 2 * (int64_t)t + (i >> 1);
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const int64_t n = (int64_t)tn * kX6BN + 64 * w + 32 * c + (lane & 31);
-          const float s_a2 = a2[c] + __shfl_xor(a2[c], 32, 64);
-          if (n < N && 64 * st < M) {
-            float* dst = stats + st * (K + 1) * lds_ + n;
-            if (lane < 32) dst[0] = s_a2;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-              const int kk = acc_row(e, lane);
-              if (kk < K) dst[(int64_t)(1 + kk) * lds_] = sq[c][e] * s_unscale;
-            }
-          }
-        }
-      }
-    }
-    return;
-  }
-  float a2[2], qm[2][KMAX];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const int64_t nb = 8 * (int64_t)tn + 2 * w + c;
-      const int64_t mk = 8 * (int64_t)t + 2 * i;
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = acc[i][c][8 * s2 + j];
-        store_split(Afr + ((nb * nmk + mk + s2) * 3) * 64 + lane, v);
-      }
-    }
-    if (!stats) continue;
-    if ((i & 1) == 0) {
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        a2[c] = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < KMAX; ++kk) qm[c][kk] = 0.f;
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int lr = 32 * i + acc_row(e, lane);
-      const float v0 = acc[i][0][e], v1 = acc[i][1][e];
-      a2[0] = fmaf(v0, v0, a2[0]);
-      a2[1] = fmaf(v1, v1, a2[1]);
-#pragma unroll
-      for (int kk = 0; kk < KMAX; ++kk) {
-        const float q = sQ[lr * KMAX + kk];
-        qm[0][kk] = fmaf(v0, q, qm[0][kk]);
-        qm[1][kk] = fmaf(v1, q, qm[1][kk]);
-      }
-    }
-    if (i & 1) {
-      const int64_t st = 2 * (int64_t)t + (i >> 1);
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const int64_t n = (int64_t)tn * kX6BN + 64 * w + 32 * c + (lane & 31);
-        const float s_a2 = a2[c] + __shfl_xor(a2[c], 32, 64);
-        float s_qm[KMAX];
-#pragma unroll
-        for (int kk = 0; kk < KMAX; ++kk) s_qm[kk] = qm[c][kk] + __shfl_xor(qm[c][kk], 32, 64);
-        if (lane < 32 && n < N && 64 * st < M) {
-          float* dst = stats + st * (K + 1) * lds_ + n;
-          dst[0] = s_a2;
-#pragma unroll
-          for (int kk = 0; kk < KMAX; ++kk)
-            if (kk < K) dst[(int64_t)(1 + kk) * lds_] = s_qm[kk];
-        }
-      }
-    }
-  }
-}
-
-// One workgroup per (pair of row tiles t, nT - 1 - t; column tile tn): the
-// pair holds 8 t + 8 + 8 (nT - t) = 8 nT + 16 k-steps whatever t, so every
-// workgroup has the same work; both items read the same Kuf column slab.  Odd
-// nT: the middle row tile is an item alone.  (c3: 385 us vs 439 us for one item
-// per workgroup, whose register count stays below 256 without spills.)
-template <int KMAX, bool F16OUT = false, bool F16IN = false, bool X8OUT = false>
-__global__ __launch_bounds__(256, 2) void trsm_stats_x6_kernel(
-    const bf16x8* __restrict__ Tfr, uint32_t tfr_bytes, const bf16x8* __restrict__ Kfr, uint32_t kfr_bytes,
-    int nmk, int nTn, int64_t M, int64_t N, const float* __restrict__ q_mu, int64_t ldq, int K,
-    bf16x8* __restrict__ Afr, float* __restrict__ stats, int64_t lds_, float* __restrict__ Af32, int64_t lda,
-    const float* __restrict__ a_var, float* __restrict__ a_bound, const float* __restrict__ t_bound = nullptr,
-    const float* __restrict__ k_bound = nullptr) {
-  __shared__ bf16x8 sL[2][4 * 3 * 64];
-  __shared__ float sQ[128 * KMAX + 1];  // + the tile's max |q_mu| (F16OUT)
-  const int nT = nmk / 8, nP = (nT + 1) / 2;
-  int p, tn;
-  if constexpr (F16OUT)
-    if (blockIdx.x == 0 && threadIdx.x == 0) *a_bound = sqrtf(*a_var);
-  col_major_item(blockIdx.x, nP, nTn, p, tn);
-  if (threadIdx.x == 0) sQ[128 * KMAX] = 0.f;
-  __syncthreads();
-  trsm_stats_x6_item<KMAX, F16OUT, F16IN, X8OUT>(sL, sQ, nT - 1 - p, tn, Tfr, tfr_bytes, Kfr, kfr_bytes, nmk, M, N, q_mu,
-                                          ldq, K, Afr, stats, lds_, Af32, lda, a_var, t_bound, k_bound);
-  if (nT - 1 - p == p) return;
-  __syncthreads();  // the epilogue's sQ reads before the next item's sQ stores
-  if (threadIdx.x == 0) sQ[128 * KMAX] = 0.f;
-  __syncthreads();
-  trsm_stats_x6_item<KMAX, F16OUT, F16IN, X8OUT>(sL, sQ, p, tn, Tfr, tfr_bytes, Kfr, kfr_bytes, nmk, M, N, q_mu, ldq, K,
-                                          Afr, stats, lds_, Af32, lda, a_var, t_bound, k_bound);
-}
-
-// ------------------------------------------------------------------ K4 (split-f16) on 16x16x32 MFMAs
-// trsm_stats_x6_item<KMAX, true, true> on x6_mainloop16 (as expert_cond16_kernel is K5 on
-// it): the same items, images, outputs and bounds.  Epilogue per 16-row block ib (k-step
-// 8 t + ib of A's image): the image fragment of each 32-column block from two lanes of the
-// 16x16 accumulator layout (one exchange across the lane halves, as K5's C_k images);
-// sum A^2 straight from the accumulators; the q_mu^T A stats of each 64-row stats tile on
-// 16x16x32 f16 MFMAs whose B operand is the accumulators themselves: lane (i, q) slot j
-// holds row 4q + j (j < 4) of block ib and row 4q + j - 4 of block ib + 1 -- any k order
-// shared by both operands is the same sum, so the split q_mu operand (from LDS) is built
-// in that order and no exchange is needed.  Rows kk of the 16 x 16 stats block are q_mu's
-// columns (KMAX <= 16).
-__device__ __forceinline__ void store_acc16_f32(const floatx4v (&acc)[8][4], float* __restrict__ out, int64_t ld,
-                                                int64_t i0, int64_t n0, int64_t M, int64_t N) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, li = lane & 15, q = lane >> 4;
-  const __amdgpu_buffer_rsrc_t r =
-      __builtin_amdgcn_make_buffer_rsrc((void*)out, (short)0, (int)(uint32_t)(M * ld * 4), 0x00020000);
-  const uint32_t soff = (uint32_t)((i0 * ld + n0) * 4);
-  const uint32_t ld32 = (uint32_t)ld;
-#pragma unroll
-  for (int cb = 0; cb < 4; ++cb) {
-    const int nl = 64 * w + 16 * cb + li;
-    if (n0 + nl < N) {
-#pragma unroll
-      for (int ib = 0; ib < 8; ++ib)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const uint32_t rl = (uint32_t)(16 * ib + 4 * q + e);
-          // (through a float: __builtin_bit_cast of the vector element lvalue itself
-          // reads element 0 with this compiler)
-          const float x = acc[ib][cb][e];
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, x), r, (rl * ld32 + (uint32_t)nl) * 4u,
-                                                soff, 0);
-        }
-    }
-  }
-}
-
-template <int KMAX>
-__device__ __forceinline__ void trsm_stats16_item(
-    bf16x8 (*sL)[4 * 2 * 3 * 64], float* __restrict__ sQ, int t, int tn, const bf16x8* __restrict__ Tfr,
-    uint32_t tfr_bytes, const bf16x8* __restrict__ Kfr, uint32_t kfr_bytes, int nmk, int64_t M, int64_t N,
-    const float* __restrict__ q_mu, int64_t ldq, int K, bf16x8* __restrict__ Afr, float* __restrict__ stats,
-    int64_t lds_, float* __restrict__ Af32, int64_t lda, const float* __restrict__ a_var,
-    const float* __restrict__ t_bound, const float* __restrict__ k_bound, int sidx = -1, int sbase = 0) {
-  static_assert(KMAX <= 16, "the stats block has 16 rows");
-  const int lane = threadIdx.x & 63, li = lane & 15, q = lane >> 4;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t i0 = 128 * (int64_t)t;
-  const float a_scale = ldexpf(1.f, img_exp(sqrtf(*a_var)));
-  // q_mu rows of the tile -> LDS [128][KMAX] and max |q_mu| (published by the main loop's barriers)
-  if (stats) {
-    float qmax = 0.f;
-    for (int idx = threadIdx.x; idx < 128 * KMAX; idx += 256) {
-      const int r = idx / KMAX, kk = idx % KMAX;
-      const float qv = (i0 + r < M && kk < K) ? q_mu[(i0 + r) * ldq + kk] : 0.f;
-      sQ[idx] = qv;
-      qmax = fmaxf(qmax, fabsf(qv));
-    }
-    qmax = wave_max_f32(qmax);
-    if (lane == 0) atomicMax(reinterpret_cast<unsigned int*>(sQ + 128 * KMAX), __float_as_uint(qmax));
-  }
-  floatx4v acc[8][4];
-  x6_mainloop16<2, 2, true>(acc, sL, img_rsrc(Tfr, tfr_bytes), (uint32_t)(4 * t * nmk) * 3u * kFragBytes,
-                            img_rsrc(Kfr, kfr_bytes), (uint32_t)((8 * tn + 2 * w) * nmk) * 3u * kFragBytes, 0,
-                            4 * t + 4, nmk);
-  K4STAMP(sidx, sbase);
-  {
-    const float unscale = ldexpf(1.f, -(img_exp(*t_bound) + img_exp(*k_bound)));
-#pragma unroll
-    for (int ib = 0; ib < 8; ++ib)
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[ib][cb][e] *= unscale;
-  }
-  if (Af32) store_acc16_f32(acc, Af32, lda, i0, (int64_t)tn * kX6BN, M, N);
-  // A's image: fragment (column block 8 tn + 2 w + c, k-step 8 t + ib), lane position pos
-  const bool lo_half = lane < 32;
-  const int pos = lo_half ? li + 32 * q : 16 + li + 32 * (q - 2);
-  if (!stats) {  // no stats: the image alone
-#pragma unroll
-    for (int ib = 0; ib < 8; ++ib)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        float v[8];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          v[r] = acc[ib][2 * c][r];
-          v[4 + r] = acc[ib][2 * c + 1][r];
-          lane_half_swap(v[r], v[4 + r]);
-        }
-        store_split_f16(Afr + ((((int64_t)8 * tn + 2 * w + c) * nmk + 8 * t + ib) * 3) * 64 + pos, v, a_scale);
-      }
-    return;
-  }
-  // With the stats: every accumulator value is split once (x = a 2^e -> f16 hi, f16 lo,
-  // packed two per dword) and both the image fragments and the stats products' B
-  // operand are assembled from the packed halves (the image's lane-half exchange moves
-  // packed halves); row-block pairs (ib0, ib0 + 1) = 64-row stats tile ib0 / 4.
-  const int qe = img_exp(__uint_as_float(reinterpret_cast<const unsigned int*>(sQ)[128 * KMAX]));
-  const float q_scale = ldexpf(1.f, qe), s_unscale = ldexpf(1.f, -(qe + img_exp(sqrtf(*a_var))));
-  floatx4v sq[4];
-  float a2[4];
-#pragma unroll
-  for (int pr4 = 0; pr4 < 4; ++pr4) {  // row blocks ib0 = 2 pr4, ib0 + 1
-    const int ib0 = 2 * pr4, st2 = pr4 >> 1;
-    if ((pr4 & 1) == 0) {
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb) {
-        sq[cb] = floatx4v{0.f, 0.f, 0.f, 0.f};
-        a2[cb] = 0.f;
-      }
-    }
-    uint32_t hp[2][4][2], lp[2][4][2];  // [row block of the pair][column block][dword]
-#pragma unroll
-    for (int d = 0; d < 2; ++d)
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-          const float a0 = acc[ib0 + d][cb][2 * h2], a1 = acc[ib0 + d][cb][2 * h2 + 1];
-          a2[cb] = fmaf(a1, a1, fmaf(a0, a0, a2[cb]));
-          const float x0 = a0 * a_scale, x1 = a1 * a_scale;
-          const _Float16 h0 = (_Float16)x0, h1 = (_Float16)x1;
-          const halfx2 hh = {h0, h1}, ll = {(_Float16)(x0 - (float)h0), (_Float16)(x1 - (float)h1)};
-          hp[d][cb][h2] = __builtin_bit_cast(uint32_t, hh);
-          lp[d][cb][h2] = __builtin_bit_cast(uint32_t, ll);
-        }
-    // the image fragments of row blocks ib0, ib0 + 1
-#pragma unroll
-    for (int d = 0; d < 2; ++d)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        // lanes 0-31: (own block 2c, lane + 32's 2c); 32-63: (lane - 32's 2c + 1, own 2c + 1)
-        uint32_t h0[2], h1[2], l0[2], l1[2];
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-          h0[h2] = hp[d][2 * c][h2];
-          h1[h2] = hp[d][2 * c + 1][h2];
-          l0[h2] = lp[d][2 * c][h2];
-          l1[h2] = lp[d][2 * c + 1][h2];
-          lane_half_swap(h0[h2], h1[h2]);
-          lane_half_swap(l0[h2], l1[h2]);
-        }
-        const u32x4v fh = u32x4v{h0[0], h0[1], h1[0], h1[1]};
-        const u32x4v fl = u32x4v{l0[0], l0[1], l1[0], l1[1]};
-        bf16x8* dst = Afr + ((((int64_t)8 * tn + 2 * w + c) * nmk + 8 * t + ib0 + d) * 3) * 64 + pos;
-#if MGP_K4_STORE_NT   // streaming stores: fewer dirty L2 lines for the kernel boundary
-        __builtin_nontemporal_store(__builtin_bit_cast(bf16x8, fh), dst);
-        __builtin_nontemporal_store(__builtin_bit_cast(bf16x8, fl), dst + 64);
-#else
-        dst[0] = __builtin_bit_cast(bf16x8, fh);
-        dst[64] = __builtin_bit_cast(bf16x8, fl);
-#endif
-      }
-    // q_mu^T A of this row-block pair: B operand slot j = row 4q + j of block ib0 (j < 4),
-    // row 4q + j - 4 of block ib0 + 1
-    bf16x8 qf[3];
-    {
-      halfx8 qh, ql;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int row = 16 * ib0 + (j < 4 ? 4 * q + j : 16 + 4 * q + j - 4);
-        const float x = (li < K ? sQ[row * KMAX + (li < KMAX ? li : 0)] : 0.f) * q_scale;
-        const _Float16 xh = (_Float16)x;
-        qh[j] = xh;
-        ql[j] = (_Float16)(x - (float)xh);
-      }
-      qf[0] = __builtin_bit_cast(bf16x8, qh);
-      qf[1] = __builtin_bit_cast(bf16x8, ql);
-    }
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) {
-      const bf16x8 bf[3] = {__builtin_bit_cast(bf16x8, u32x4v{hp[0][cb][0], hp[0][cb][1], hp[1][cb][0], hp[1][cb][1]}),
-                            __builtin_bit_cast(bf16x8, u32x4v{lp[0][cb][0], lp[0][cb][1], lp[1][cb][0], lp[1][cb][1]}),
-                            bf16x8{}};
-      sq[cb] = mfma16_fmt<2, true>(qf, bf, sq[cb]);
-    }
-    if ((pr4 & 1) == 1) {  // 64-row stats tile 2 t + st2 done
-      const int64_t st = 2 * (int64_t)t + st2;
-      if (64 * st < M) {
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) {
-          const int64_t n = (int64_t)tn * kX6BN + 64 * w + 16 * cb + li;
-          float s_a2 = a2[cb] + lane_xor16(a2[cb]);
-          s_a2 += lane_xor32(s_a2);
-          if (n < N) {
-            float* dst = stats + st * (K + 1) * lds_ + n;
-            if (lane < 16) dst[0] = s_a2;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const int kk = 4 * q + e;
-              if (kk < K) dst[(int64_t)(1 + kk) * lds_] = sq[cb][e] * s_unscale;
-            }
-          }
-        }
-      }
-    }
-  }
-}
-
-// Row-tile pairs as trsm_stats_x6_kernel (equal work per workgroup).
-template <int KMAX>
-__global__ __launch_bounds__(256, 2) void trsm_stats16_kernel(
-    const bf16x8* __restrict__ Tfr, uint32_t tfr_bytes, const bf16x8* __restrict__ Kfr, uint32_t kfr_bytes,
-    int nmk, int nTn, int64_t M, int64_t N, const float* __restrict__ q_mu, int64_t ldq, int K,
-    bf16x8* __restrict__ Afr, float* __restrict__ stats, int64_t lds_, float* __restrict__ Af32, int64_t lda,
-    const float* __restrict__ a_var, float* __restrict__ a_bound, const float* __restrict__ t_bound,
-    const float* __restrict__ k_bound) {
-  __shared__ bf16x8 sL[2][4 * 2 * 3 * 64];
-  __shared__ float sQ[128 * KMAX + 1];
-  const int nT = nmk / 8, nP = (nT + 1) / 2;
-  int p, tn;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *a_bound = sqrtf(*a_var);
-  col_major_item(blockIdx.x, nP, nTn, p, tn);
-  const int it = blockIdx.x;  // debug stamps only
-  K4STAMP(it, 0);
-  if (threadIdx.x == 0) sQ[128 * KMAX] = 0.f;
-  __syncthreads();
-  trsm_stats16_item<KMAX>(sL, sQ, nT - 1 - p, tn, Tfr, tfr_bytes, Kfr, kfr_bytes, nmk, M, N, q_mu, ldq, K, Afr, stats,
-                          lds_, Af32, lda, a_var, t_bound, k_bound, it, 1);
-  K4STAMP(it, 2);
-  if (nT - 1 - p == p) return;
-  __syncthreads();
-  if (threadIdx.x == 0) sQ[128 * KMAX] = 0.f;
-  __syncthreads();
-  trsm_stats16_item<KMAX>(sL, sQ, p, tn, Tfr, tfr_bytes, Kfr, kfr_bytes, nmk, M, N, q_mu, ldq, K, Afr, stats, lds_,
-                          Af32, lda, a_var, t_bound, k_bound, it, 3);
-  K4STAMP(it, 4);
-}
-
-// One layer's operands of the batched K4 (both SMGP layers share M, N and K).
-struct K4Layer {
-  const bf16x8* Tfr;
-  const bf16x8* Kfr;
-  const float* q_mu;
-  bf16x8* Afr;
-  float* stats;
-  float* Af32;
-  const float* a_var;
-  float* a_bound;
-  const float* t_bound;
-  const float* k_bound;
-  int64_t ldq, lds, lda;
-};
-
-// trsm_stats16_kernel over two layers in one launch: workgroups [0, per) run layer 0's
-// items, [per, 2 per) layer 1's, each exactly as the one-layer kernel does (same items,
-// same arithmetic: bit-identical images and statistics).  One launch instead of two
-// drops a dispatch round boundary and a kernel tail between the layers.
-template <int KMAX>
-__global__ __launch_bounds__(256, 2) void trsm_stats16_pair_kernel(K4Layer l0, K4Layer l1, int per,
-                                                                  uint32_t tfr_bytes, uint32_t kfr_bytes, int nmk,
-                                                                  int nTn, int64_t M, int64_t N, int K) {
-  __shared__ bf16x8 sL[2][4 * 2 * 3 * 64];
-  __shared__ float sQ[128 * KMAX + 1];
-  const bool second = (int)blockIdx.x >= per;
-  const K4Layer& l = second ? l1 : l0;
-  const int bid = (int)blockIdx.x - (second ? per : 0);
-  const int nT = nmk / 8, nP = (nT + 1) / 2;
-  int p, tn;
-  if (bid == 0 && threadIdx.x == 0) *l.a_bound = sqrtf(*l.a_var);
-  col_major_item(bid, nP, nTn, p, tn);
-  if (threadIdx.x == 0) sQ[128 * KMAX] = 0.f;
-  __syncthreads();
-  trsm_stats16_item<KMAX>(sL, sQ, nT - 1 - p, tn, l.Tfr, tfr_bytes, l.Kfr, kfr_bytes, nmk, M, N, l.q_mu, l.ldq, K,
-                          l.Afr, l.stats, l.lds, l.Af32, l.lda, l.a_var, l.t_bound, l.k_bound);
-  if (nT - 1 - p == p) return;
-  __syncthreads();
-  if (threadIdx.x == 0) sQ[128 * KMAX] = 0.f;
-  __syncthreads();
-  trsm_stats16_item<KMAX>(sL, sQ, p, tn, l.Tfr, tfr_bytes, l.Kfr, kfr_bytes, nmk, M, N, l.q_mu, l.ldq, K, l.Afr,
-                          l.stats, l.lds, l.Af32, l.lda, l.a_var, l.t_bound, l.k_bound);
-}
-
 }  // namespace mgp
 
 using namespace mgp;
-
-extern "C" size_t mgp_expert_x6_workspace_bytes(int64_t M, int64_t N, int32_t K) {
-  if (M <= 0 || N <= 0 || K <= 0) return 16;
-  return (size_t)K * (size_t)(x6_mp(M) / kX6BM) * (size_t)((N + 3) / 4 * 4) * sizeof(float);
-}
-
-// Argument checks report the index in mgp_expert_conditional_x6's signature.
-static int expert_cond_planes(const void* Afr, size_t afr_bytes, const void* Lfr, size_t lfr_bytes,
-                              const float* stats, int64_t lds, const float* variance, int64_t M, int64_t N,
-                              int32_t K, int planes, float* fmean, float* fvar, int64_t ldf, void* workspace,
-                              size_t workspace_bytes, mgp_stream_t stream, bool f16 = false,
-                              bool x8 = false, void* Cfr = nullptr, size_t cfr_bytes = 0,
-                              const float* colmax = nullptr) {
-  if (!Afr) return -1;
-  if (afr_bytes < mgp_x6_cols_bytes(M, N)) return -2;
-  if (!Lfr) return -3;
-  if (lfr_bytes < mgp_x6_lower_bytes(M, K)) return -4;
-  if (!stats) return -5;
-  if (lds < N) return -6;
-  if (!variance) return -7;
-  if (M < 0) return -8;
-  if (N < 0) return -9;
-  if (K < 1) return -10;
-  if (!fmean) return -11;
-  if (!fvar) return -12;
-  if (ldf < N) return -13;
-  if (!aligned16(Afr) || !aligned16(Lfr)) return MGP_ERR_ALIGN;
-  if (afr_bytes >= ((size_t)1 << 32) || lfr_bytes >= ((size_t)1 << 32)) return MGP_ERR_UNSUPPORTED;
-  if (M == 0 || N == 0) return MGP_OK;
-  if (!workspace || workspace_bytes < mgp_expert_x6_workspace_bytes(M, N, K)) return MGP_ERR_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t Mp = x6_mp(M);
-  const int nmk = (int)(Mp / 16), nmb = (int)(Mp / 32), nTp = (int)(Mp / kX6BM);
-  const int nTn = (int)(x6_np(N) / kX6BN);
-  const int64_t ldp = (N + 3) / 4 * 4;
-  float* part = (float*)workspace;
-  const dim3 grid((unsigned)(K * nTp * nTn));
-  const float* a_bound = trailer(const_cast<void*>(Afr), cols_planes(M, N));
-  const float* l_bound = trailer(const_cast<void*>(Lfr), lower_planes(M, K));
-#define MGP_K5_CASE(NP, F16, X8)                                                                        \
-  if (planes == NP && f16 == F16 && x8 == X8)                                                           \
-    hipLaunchKernelGGL((expert_cond_x6_kernel<NP, F16, X8>), grid, dim3(256), 0, s, (const bf16x8*)Afr, \
-                       (const bf16x8*)Lfr, (uint32_t)mgp_x6_cols_bytes(M, N),                           \
-                       (uint32_t)mgp_x6_lower_bytes(M, K), nmk, nmb, nTn, K, N, part, ldp, a_bound,     \
-                       l_bound);
-  if (Cfr) {  // training: + the C_k images (mgp_expert_conditional_f16c)
-    if (!f16 || x8 || planes != 2) return MGP_ERR_UNSUPPORTED;
-    if (!colmax) return -18;
-    const size_t cexp = cols_planes(M, N);
-    if (cfr_bytes < (size_t)K * cexp) return -17;
-    if (!aligned16(Cfr)) return MGP_ERR_ALIGN;
-    hipLaunchKernelGGL((expert_cond16_kernel<true>), grid, dim3(256), 0, s, (const bf16x8*)Afr, (const bf16x8*)Lfr,
-                       (uint32_t)mgp_x6_cols_bytes(M, N), (uint32_t)mgp_x6_lower_bytes(M, K), nmk, nmb, nTn, K, N,
-                       part, ldp, a_bound, l_bound, (bf16x8*)Cfr, (int64_t)(cexp / 16), colmax);
-  } else if (planes == 2 && f16 && !x8) {  // the split-f16 forward K5 (16x16x32 MFMA)
-    hipLaunchKernelGGL((expert_cond16_kernel<false>), grid, dim3(256), 0, s, (const bf16x8*)Afr, (const bf16x8*)Lfr,
-                       (uint32_t)mgp_x6_cols_bytes(M, N), (uint32_t)mgp_x6_lower_bytes(M, K), nmk, nmb, nTn, K, N,
-                       part, ldp, a_bound, l_bound);
-  } else {
-  MGP_K5_CASE(3, false, false)
-  MGP_K5_CASE(2, false, false)
-  MGP_K5_CASE(1, false, false)
-  MGP_K5_CASE(2, true, true)
-  }
-#undef MGP_K5_CASE
-  int st = launch_status();
-  if (st) return st;
-  return mgp_launch_cond_finalize(stats, lds, mgp_stats_tiles(M), part, ldp, nTp, variance, N, K, fmean, fvar,
-                                  ldf, s);
-}
-
-extern "C" int mgp_expert_conditional_x6(const void* Afr, size_t afr_bytes, const void* Lfr, size_t lfr_bytes,
-                                         const float* stats, int64_t lds, const float* variance, int64_t M,
-                                         int64_t N, int32_t K, float* fmean, float* fvar, int64_t ldf,
-                                         void* workspace, size_t workspace_bytes, mgp_stream_t stream) {
-  return expert_cond_planes(Afr, afr_bytes, Lfr, lfr_bytes, stats, lds, variance, M, N, K, 3, fmean, fvar, ldf,
-                            workspace, workspace_bytes, stream);
-}
-
-extern "C" int mgp_expert_conditional_planes(const void* Afr, size_t afr_bytes, const void* Lfr, size_t lfr_bytes,
-                                             const float* stats, int64_t lds, const float* variance, int64_t M,
-                                             int64_t N, int32_t K, int32_t planes, float* fmean, float* fvar,
-                                             int64_t ldf, void* workspace, size_t workspace_bytes,
-                                             mgp_stream_t stream) {
-  if (planes < 1 || planes > 3) return -11;
-  const int st = expert_cond_planes(Afr, afr_bytes, Lfr, lfr_bytes, stats, lds, variance, M, N, K, planes, fmean,
-                                    fvar, ldf, workspace, workspace_bytes, stream);
-  return (st <= -11 && st >= -13) ? st - 1 : st;  // fmean, fvar, ldf follow `planes` here
-}
-
-template <int KMAX>
-static int launch_trsm_x6(const void* Tfr, size_t tb, const void* Kfr, size_t kb, int64_t M, int64_t N,
-                          const float* q_mu, int64_t ldq, int K, void* Afr, float* stats, int64_t lds,
-                          float* A, int64_t lda, hipStream_t s, const float* a_var = nullptr,
-                          bool f16in = false, bool x8 = false) {
-  const int64_t Mp = x6_mp(M);
-  const int nmk = (int)(Mp / 16), nT = (int)(Mp / kX6BM), nTn = (int)(x6_np(N) / kX6BN);
-  const dim3 grid((unsigned)((nT + 1) / 2 * nTn));
-  float* a_bound = trailer(Afr, cols_planes(M, N));
-  if (f16in) {
-    const float* t_bound = trailer(const_cast<void*>(Tfr), lower_planes(M, 1));
-    const float* k_bound = trailer(const_cast<void*>(Kfr), cols_planes(M, N));
-    if (x8)
-      hipLaunchKernelGGL((trsm_stats_x6_kernel<KMAX, true, true, true>), grid, dim3(256), 0, s, (const bf16x8*)Tfr,
-                         (uint32_t)tb, (const bf16x8*)Kfr, (uint32_t)kb, nmk, nTn, M, N, q_mu, ldq, K,
-                         (bf16x8*)Afr, stats, lds, A, lda, a_var, a_bound, t_bound, k_bound);
-    else
-      hipLaunchKernelGGL((trsm_stats16_kernel<KMAX>), grid, dim3(256), 0, s, (const bf16x8*)Tfr, (uint32_t)tb,
-                         (const bf16x8*)Kfr, (uint32_t)kb, nmk, nTn, M, N, q_mu, ldq, K, (bf16x8*)Afr, stats, lds, A,
-                         lda, a_var, a_bound, t_bound, k_bound);
-  } else if (a_var)
-    hipLaunchKernelGGL((trsm_stats_x6_kernel<KMAX, true>), grid, dim3(256), 0, s, (const bf16x8*)Tfr,
-                       (uint32_t)tb, (const bf16x8*)Kfr, (uint32_t)kb, nmk, nTn, M, N, q_mu, ldq, K,
-                       (bf16x8*)Afr, stats, lds, A, lda, a_var, a_bound);
-  else
-    hipLaunchKernelGGL((trsm_stats_x6_kernel<KMAX, false>), grid, dim3(256), 0, s, (const bf16x8*)Tfr,
-                       (uint32_t)tb, (const bf16x8*)Kfr, (uint32_t)kb, nmk, nTn, M, N, q_mu, ldq, K,
-                       (bf16x8*)Afr, stats, lds, A, lda, a_var, a_bound);
-  return launch_status();
-}
-
-extern "C" int mgp_trsm_stats_x6(const void* Tfr, size_t tfr_bytes, const void* Kfr, size_t kfr_bytes,
-                                 int64_t M, int64_t N, const float* q_mu, int64_t ldq, int32_t K,
-                                 void* Afr, size_t afr_bytes, float* stats, int64_t lds, float* A,
-                                 int64_t lda, mgp_stream_t stream) {
-  if (!Tfr) return -1;
-  if (tfr_bytes < mgp_x6_lower_bytes(M, 1)) return -2;
-  if (!Kfr) return -3;
-  if (kfr_bytes < mgp_x6_cols_bytes(M, N)) return -4;
-  if (M < 0) return -5;
-  if (N < 0) return -6;
-  if (!q_mu) return -7;
-  if (ldq < K) return -8;
-  if (K < 1) return -9;
-  if (K > 16) return MGP_ERR_UNSUPPORTED;
-  if (!Afr) return -10;
-  if (afr_bytes < mgp_x6_cols_bytes(M, N)) return -11;
-  if (stats && lds < N) return -13;
-  if (A && lda < N) return -15;
-  if (!aligned16(Tfr) || !aligned16(Kfr) || !aligned16(Afr)) return MGP_ERR_ALIGN;
-  if (mgp_x6_cols_bytes(M, N) >= ((size_t)1 << 32) || mgp_x6_lower_bytes(M, 1) >= ((size_t)1 << 32))
-    return MGP_ERR_UNSUPPORTED;
-  if (M == 0 || N == 0) return MGP_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const size_t tb = mgp_x6_lower_bytes(M, 1), kb = mgp_x6_cols_bytes(M, N);
-  if (K <= 4) return launch_trsm_x6<4>(Tfr, tb, Kfr, kb, M, N, q_mu, ldq, K, Afr, stats, lds, A, lda, s);
-  if (K <= 8) return launch_trsm_x6<8>(Tfr, tb, Kfr, kb, M, N, q_mu, ldq, K, Afr, stats, lds, A, lda, s);
-  return launch_trsm_x6<16>(Tfr, tb, Kfr, kb, M, N, q_mu, ldq, K, Afr, stats, lds, A, lda, s);
-}
-
-// ------------------------------------------------------------------ split-f16 ("f16x3") K5 path
-static int trsm_stats_f16_out(const void* Tfr, size_t tfr_bytes, const void* Kfr, size_t kfr_bytes, int64_t M,
-                              int64_t N, const float* q_mu, int64_t ldq, int32_t K, const float* variance, void* Afr,
-                              size_t afr_bytes, float* stats, int64_t lds, mgp_stream_t stream, bool f16in,
-                              float* A = nullptr, int64_t lda = 0, bool x8 = false) {
-  if (!Tfr) return -1;
-  if (tfr_bytes < mgp_x6_lower_bytes(M, 1)) return -2;
-  if (!Kfr) return -3;
-  if (kfr_bytes < mgp_x6_cols_bytes(M, N)) return -4;
-  if (M < 0) return -5;
-  if (N < 0) return -6;
-  if (!q_mu) return -7;
-  if (ldq < K) return -8;
-  if (K < 1) return -9;
-  if (K > 16) return MGP_ERR_UNSUPPORTED;
-  if (!variance) return -10;
-  if (!Afr) return -11;
-  if (afr_bytes < mgp_x6_cols_bytes(M, N)) return -12;
-  if (stats && lds < N) return -14;  // stats may be NULL (A image only)
-  
-  if (!aligned16(Tfr) || !aligned16(Kfr) || !aligned16(Afr)) return MGP_ERR_ALIGN;
-  if (mgp_x6_cols_bytes(M, N) >= ((size_t)1 << 32) || mgp_x6_lower_bytes(M, 1) >= ((size_t)1 << 32))
-    return MGP_ERR_UNSUPPORTED;
-  if (M == 0 || N == 0) return MGP_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const size_t tb = mgp_x6_lower_bytes(M, 1), kb = mgp_x6_cols_bytes(M, N);
-  if (K <= 4)
-    return launch_trsm_x6<4>(Tfr, tb, Kfr, kb, M, N, q_mu, ldq, K, Afr, stats, lds, A, lda, s, variance, f16in, x8);
-  if (K <= 8)
-    return launch_trsm_x6<8>(Tfr, tb, Kfr, kb, M, N, q_mu, ldq, K, Afr, stats, lds, A, lda, s, variance, f16in, x8);
-  return launch_trsm_x6<16>(Tfr, tb, Kfr, kb, M, N, q_mu, ldq, K, Afr, stats, lds, A, lda, s, variance, f16in, x8);
-}
-
-// x6 images in (Tfr, Kfr), split-f16 A image out (K5's operand).
-extern "C" int mgp_trsm_stats_x6_f16(const void* Tfr, size_t tfr_bytes, const void* Kfr, size_t kfr_bytes,
-                                     int64_t M, int64_t N, const float* q_mu, int64_t ldq, int32_t K,
-                                     const float* variance, void* Afr, size_t afr_bytes, float* stats,
-                                     int64_t lds, mgp_stream_t stream) {
-  return trsm_stats_f16_out(Tfr, tfr_bytes, Kfr, kfr_bytes, M, N, q_mu, ldq, K, variance, Afr, afr_bytes, stats, lds,
-                            stream, false);
-}
-
-// split-f16 images in (mgp_split_upper_f16, mgp_rbf_kuf_f16) and out: three f16
-// products per block instead of six bf16 ones.
-extern "C" int mgp_trsm_stats_f16(const void* Tfr, size_t tfr_bytes, const void* Kfr, size_t kfr_bytes, int64_t M,
-                                  int64_t N, const float* q_mu, int64_t ldq, int32_t K, const float* variance,
-                                  void* Afr, size_t afr_bytes, float* stats, int64_t lds, float* A, int64_t lda,
-                                  mgp_stream_t stream) {
-  if (A && lda < N) return -16;
-  return trsm_stats_f16_out(Tfr, tfr_bytes, Kfr, kfr_bytes, M, N, q_mu, ldq, K, variance, Afr, afr_bytes, stats, lds,
-                            stream, true, A, lda);
-}
-
-// mgp_trsm_stats_f16 for `batch` (1 or 2) layers of equal M, N, K in one launch (the two
-// SMGP layers' K4); the per-layer operands are host arrays of device pointers (A[b] may be
-// NULL; A itself may be NULL: no f32 A for any layer).  Results are bit-identical to one
-// mgp_trsm_stats_f16 call per layer.  Errors: the single call's codes for the first bad
-// layer; -17 for a batch outside [1, 2].
-extern "C" int mgp_trsm_stats_f16_batch(int32_t batch, const void* const* Tfr, size_t tfr_bytes,
-                                        const void* const* Kfr, size_t kfr_bytes, int64_t M, int64_t N,
-                                        const float* const* q_mu, int64_t ldq, int32_t K,
-                                        const float* const* variance, void* const* Afr, size_t afr_bytes,
-                                        float* const* stats, int64_t lds, float* const* A, int64_t lda,
-                                        mgp_stream_t stream) {
-  if (batch < 1 || batch > 2) return -17;
-  if (!Tfr || !Kfr || !q_mu || !variance || !Afr || !stats) return -1;
-  if (A && lda < N) return -16;
-  for (int b = 0; b < batch; ++b) {
-    if (!Tfr[b]) return -1;
-    if (tfr_bytes < mgp_x6_lower_bytes(M, 1)) return -2;
-    if (!Kfr[b]) return -3;
-    if (kfr_bytes < mgp_x6_cols_bytes(M, N)) return -4;
-    if (M < 0) return -5;
-    if (N < 0) return -6;
-    if (!q_mu[b]) return -7;
-    if (ldq < K) return -8;
-    if (K < 1) return -9;
-    if (K > 16) return MGP_ERR_UNSUPPORTED;
-    if (!variance[b]) return -10;
-    if (!Afr[b]) return -11;
-    if (afr_bytes < mgp_x6_cols_bytes(M, N)) return -12;
-    if (!stats[b]) return -13;
-    if (lds < N) return -14;
-    if (!aligned16(Tfr[b]) || !aligned16(Kfr[b]) || !aligned16(Afr[b])) return MGP_ERR_ALIGN;
-  }
-  if (mgp_x6_cols_bytes(M, N) >= ((size_t)1 << 32) || mgp_x6_lower_bytes(M, 1) >= ((size_t)1 << 32))
-    return MGP_ERR_UNSUPPORTED;
-  if (M == 0 || N == 0) return MGP_OK;
-  const size_t tb = mgp_x6_lower_bytes(M, 1), kb = mgp_x6_cols_bytes(M, N);
-  const int64_t Mp = x6_mp(M);
-  const int nmk = (int)(Mp / 16), nT = (int)(Mp / kX6BM), nTn = (int)(x6_np(N) / kX6BN);
-  const int per = (nT + 1) / 2 * nTn;
-  K4Layer l[2];
-  for (int b = 0; b < 2; ++b) {
-    const int s = b < batch ? b : 0;
-    l[b] = K4Layer{(const bf16x8*)Tfr[s], (const bf16x8*)Kfr[s], q_mu[s], (bf16x8*)Afr[s], stats[s],
-                   A ? A[s] : nullptr, variance[s], trailer(Afr[s], cols_planes(M, N)),
-                   trailer(const_cast<void*>(Tfr[s]), lower_planes(M, 1)),
-                   trailer(const_cast<void*>(Kfr[s]), cols_planes(M, N)), ldq, lds, lda};
-  }
-  const dim3 grid((unsigned)(per * batch));
-  hipStream_t s = (hipStream_t)stream;
-  if (K <= 4)
-    hipLaunchKernelGGL(trsm_stats16_pair_kernel<4>, grid, dim3(256), 0, s, l[0], l[1], per, (uint32_t)tb,
-                       (uint32_t)kb, nmk, nTn, M, N, (int)K);
-  else if (K <= 8)
-    hipLaunchKernelGGL(trsm_stats16_pair_kernel<8>, grid, dim3(256), 0, s, l[0], l[1], per, (uint32_t)tb,
-                       (uint32_t)kb, nmk, nTn, M, N, (int)K);
-  else
-    hipLaunchKernelGGL(trsm_stats16_pair_kernel<16>, grid, dim3(256), 0, s, l[0], l[1], per, (uint32_t)tb,
-                       (uint32_t)kb, nmk, nTn, M, N, (int)K);
-  return launch_status();
-}
-
-// mgp_trsm_stats_f16 that also writes the A image's e4m3 cross-term plane (the
-// operand of mgp_expert_conditional_f16x8).  With A == NULL the f16 lo plane is
-// not written (only the f16x8 K5 reads that image).
-extern "C" int mgp_trsm_stats_f16x8(const void* Tfr, size_t tfr_bytes, const void* Kfr, size_t kfr_bytes, int64_t M,
-                                    int64_t N, const float* q_mu, int64_t ldq, int32_t K, const float* variance,
-                                    void* Afr, size_t afr_bytes, float* stats, int64_t lds, float* A, int64_t lda,
-                                    mgp_stream_t stream) {
-  if (A && lda < N) return -16;
-  return trsm_stats_f16_out(Tfr, tfr_bytes, Kfr, kfr_bytes, M, N, q_mu, ldq, K, variance, Afr, afr_bytes, stats, lds,
-                            stream, true, A, lda, true);
-}
-
-extern "C" int mgp_expert_conditional_f16(const void* Afr, size_t afr_bytes, const void* Lfr, size_t lfr_bytes,
-                                          const float* stats, int64_t lds, const float* variance, int64_t M,
-                                          int64_t N, int32_t K, float* fmean, float* fvar, int64_t ldf,
-                                          void* workspace, size_t workspace_bytes, mgp_stream_t stream) {
-  return expert_cond_planes(Afr, afr_bytes, Lfr, lfr_bytes, stats, lds, variance, M, N, K, 2, fmean, fvar, ldf,
-                            workspace, workspace_bytes, stream, true);
-}
-
-// Training: mgp_expert_conditional_f16 that also writes C_k = L_k^T A per expert as a
-// split-f16 B-layout image (Cfr, mgp_c_images_bytes; colmax from mgp_colnorm_max
-// of q_sqrt), consumed by mgp_conditional_backward_f16c.
-extern "C" int mgp_expert_conditional_f16c(const void* Afr, size_t afr_bytes, const void* Lfr, size_t lfr_bytes,
-                                           const float* stats, int64_t lds, const float* variance, int64_t M,
-                                           int64_t N, int32_t K, float* fmean, float* fvar, int64_t ldf,
-                                           void* workspace, size_t workspace_bytes, void* Cfr, size_t cfr_bytes,
-                                           const float* colmax, mgp_stream_t stream) {
-  if (!Cfr) return -16;
-  return expert_cond_planes(Afr, afr_bytes, Lfr, lfr_bytes, stats, lds, variance, M, N, K, 2, fmean, fvar, ldf,
-                            workspace, workspace_bytes, stream, true, false, Cfr, cfr_bytes, colmax);
-}
-
-// mgp_expert_conditional_f16 (Cfr == NULL) or mgp_expert_conditional_f16c (Cfr, colmax:
-// host arrays of device pointers) for `batch` (1 or 2) layers of equal M, N, K: one K5
-// launch over both layers, then each layer's finalize.  Per-layer operands are host arrays
-// of device pointers, one workspace per layer.  Bit-identical to one call per layer.
-// Errors: the single call's codes for the first bad layer; -20 for a batch outside [1, 2].
-extern "C" int mgp_expert_conditional_f16_batch(int32_t batch, const void* const* Afr, size_t afr_bytes,
-                                                const void* const* Lfr, size_t lfr_bytes, const float* const* stats,
-                                                int64_t lds, const float* const* variance, int64_t M, int64_t N,
-                                                int32_t K, float* const* fmean, float* const* fvar, int64_t ldf,
-                                                void* const* workspace, size_t workspace_bytes,
-                                                void* const* Cfr, size_t cfr_bytes, const float* const* colmax,
-                                                mgp_stream_t stream) {
-  if (batch < 1 || batch > 2) return -20;
-  if (!Afr || !Lfr || !stats || !variance || !fmean || !fvar || !workspace) return -1;
-  const size_t cexp = cols_planes(M, N);
-  for (int b = 0; b < batch; ++b) {
-    if (!Afr[b]) return -1;
-    if (afr_bytes < mgp_x6_cols_bytes(M, N)) return -2;
-    if (!Lfr[b]) return -3;
-    if (lfr_bytes < mgp_x6_lower_bytes(M, K)) return -4;
-    if (!stats[b]) return -5;
-    if (lds < N) return -6;
-    if (!variance[b]) return -7;
-    if (M < 0) return -8;
-    if (N < 0) return -9;
-    if (K < 1) return -10;
-    if (!fmean[b]) return -11;
-    if (!fvar[b]) return -12;
-    if (ldf < N) return -13;
-    if (!aligned16(Afr[b]) || !aligned16(Lfr[b])) return MGP_ERR_ALIGN;
-    if (M > 0 && N > 0 && (!workspace[b] || workspace_bytes < mgp_expert_x6_workspace_bytes(M, N, K)))
-      return MGP_ERR_WORKSPACE;
-    if (Cfr) {
-      if (!Cfr[b]) return -16;
-      if (cfr_bytes < (size_t)K * cexp) return -17;
-      if (!colmax || !colmax[b]) return -18;
-      if (!aligned16(Cfr[b])) return MGP_ERR_ALIGN;
-    }
-  }
-  if (afr_bytes >= ((size_t)1 << 32) || lfr_bytes >= ((size_t)1 << 32)) return MGP_ERR_UNSUPPORTED;
-  if (M == 0 || N == 0) return MGP_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t Mp = x6_mp(M);
-  const int nmk = (int)(Mp / 16), nmb = (int)(Mp / 32), nTp = (int)(Mp / kX6BM);
-  const int nTn = (int)(x6_np(N) / kX6BN);
-  const int64_t ldp = (N + 3) / 4 * 4;
-  const int per = K * nTp * nTn;
-  K5Layer l[2];
-  for (int b = 0; b < 2; ++b) {
-    const int q = b < batch ? b : 0;
-    l[b] = K5Layer{(const bf16x8*)Afr[q], (const bf16x8*)Lfr[q], (float*)workspace[q],
-                   trailer(const_cast<void*>(Afr[q]), cols_planes(M, N)),
-                   trailer(const_cast<void*>(Lfr[q]), lower_planes(M, K)), Cfr ? (bf16x8*)Cfr[q] : nullptr,
-                   Cfr ? colmax[q] : nullptr};
-  }
-  const dim3 grid((unsigned)(per * batch));
-  const uint32_t ab = (uint32_t)mgp_x6_cols_bytes(M, N), lb = (uint32_t)mgp_x6_lower_bytes(M, K);
-  if (Cfr)
-    hipLaunchKernelGGL(expert_cond16_pair_kernel<true>, grid, dim3(256), 0, s, l[0], l[1], per, ab, lb, nmk, nmb, nTn,
-                       (int)K, N, ldp, (int64_t)(cexp / 16));
-  else
-    hipLaunchKernelGGL(expert_cond16_pair_kernel<false>, grid, dim3(256), 0, s, l[0], l[1], per, ab, lb, nmk, nmb,
-                       nTn, (int)K, N, ldp, (int64_t)0);
-  int st = launch_status();
-  if (st) return st;
-  if (batch == 2)   // both layers' finalize in one launch too
-    return mgp_launch_cond_finalize2(CondFinLayer{stats[0], (const float*)workspace[0], variance[0], fmean[0], fvar[0]},
-                                     CondFinLayer{stats[1], (const float*)workspace[1], variance[1], fmean[1], fvar[1]},
-                                     lds, mgp_stats_tiles(M), ldp, nTp, N, K, ldf, s);
-  return mgp_launch_cond_finalize(stats[0], lds, mgp_stats_tiles(M), (const float*)workspace[0], ldp, nTp,
-                                  variance[0], N, K, fmean[0], fvar[0], ldf, s);
-}
-
-// Split-f16 images with the X8 plane (mgp_split_lower_f16, mgp_split_cols_f16,
-// mgp_trsm_stats_f16x8): hi products on f16, cross terms on e4m3 (mfma_f8x).
-extern "C" int mgp_expert_conditional_f16x8(const void* Afr, size_t afr_bytes, const void* Lfr, size_t lfr_bytes,
-                                            const float* stats, int64_t lds, const float* variance, int64_t M,
-                                            int64_t N, int32_t K, float* fmean, float* fvar, int64_t ldf,
-                                            void* workspace, size_t workspace_bytes, mgp_stream_t stream) {
-  return expert_cond_planes(Afr, afr_bytes, Lfr, lfr_bytes, stats, lds, variance, M, N, K, 2, fmean, fvar, ldf,
-                            workspace, workspace_bytes, stream, true, true);
-}
 
 // ------------------------------------------------------------------ conditional backward (x6)
 
@@ -3171,9 +1630,3 @@ extern "C" int mgp_conditional_backward_f16x8(
                               N, K, g_q_mu, ldgq, g_q_sqrt, ldgs, strideg, g_Kuf, ldk, g_Lm, ldgl, g_var, workspace,
                               workspace_bytes, stream, true, true);
 }
-
-#ifdef MGP_DBG_STAMPS
-extern "C" int mgp_dbg_k4_stamps(unsigned long long* host) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(mgp::g_k4_stamps), sizeof(mgp::g_k4_stamps));
-}
-#endif

@@ -214,7 +214,7 @@ __device__ __forceinline__ void stash4(char* dst, floatx4 v) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     __bf16 a, b, c;
-    split3(v[j], a, b, c);
+    split_bf16x3(v[j], a, b, c);
     h[j] = a; m[j] = b; l[j] = c;
   }
   *reinterpret_cast<bf16x4*>(dst) = h;

@@ -73,7 +73,7 @@ __device__ __forceinline__ void store_fragment(bf16x8* __restrict__ dst, const f
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       __bf16 a, b, c;
-      split3(v[j], a, b, c);
+      split_bf16x3(v[j], a, b, c);
       h[j] = a; m[j] = b; l[j] = c;
     }
     img_store<POL>(dst, h);

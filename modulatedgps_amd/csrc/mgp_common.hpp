@@ -130,7 +130,7 @@ typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ int kperm(int h, int j) { return (j & 3) + 8 * (j >> 2) + 4 * h; }
 
 // x -> (hi, mid, lo) bf16 planes; both differences are exact in f32.
-__device__ __forceinline__ void split3(float x, __bf16& hi, __bf16& mid, __bf16& lo) {
+__device__ __forceinline__ void split_bf16x3(float x, __bf16& hi, __bf16& mid, __bf16& lo) {
   hi = (__bf16)x;
   const float r1 = x - (float)hi;
   mid = (__bf16)r1;
@@ -145,7 +145,7 @@ __device__ __forceinline__ void store_split(bf16x8* __restrict__ dst, const floa
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     __bf16 a, b, c;
-    split3(v[j], a, b, c);
+    split_bf16x3(v[j], a, b, c);
     h[j] = a; m[j] = b; l[j] = c;
   }
   dst[0] = h;

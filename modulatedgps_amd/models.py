@@ -15,7 +15,7 @@ arguments and method names).  The SMGP ELBO hot path
     K5 mgp_expert_conditional_f16_batch  fmean, fvar [K, N]     models.py:141-143 (LTA, fvar)
     (config expert_format "x6": the same chain on exact split-bf16 images, six bf16
      products per f32 product -- mgp_rbf_kuf_x6, mgp_split_upper_x6 / _lower_x6,
-     mgp_trsm_stats_x6, mgp_expert_conditional_x6 -- csrc/images.hip, csrc/split3.hip;
+     mgp_trsm_stats_x6, mgp_expert_conditional_x6 -- csrc/images.hip, csrc/trsm_stats.hip, csrc/expert_cond.hip;
      config.set_conditional_mode("f32"): mgp_rbf_kuf + mgp_trsm_stats +
      mgp_expert_conditional_f32 on the exact-f32 MFMA)
   K6 mgp_elbo_terms         sum_n lse_s(...)        models.py:55-67,73-76

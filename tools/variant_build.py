@@ -1,6 +1,6 @@
 """Build a variant of libmgp_hip.so with extra -D flags on one source, for A/B timing
 on the GPU box via MGP_HIP_LIB (the in-tree library is left alone).
-    python tools/variant_build.py NAME split3.hip -DFOO=1 ...   -> abvar/NAME.so (travels to the box)"""
+    python tools/variant_build.py NAME expert_cond.hip -DFOO=1 ...   -> abvar/NAME.so (travels to the box)"""
 import os
 import subprocess
 import sys
@@ -14,8 +14,9 @@ out_dir = os.path.join(B.ROOT, "abvar")
 os.makedirs(out_dir, exist_ok=True)
 obj = os.path.join(out_dir, name + "_" + src.replace(".hip", ".o"))
 subprocess.run([B.HIPCC, *B.CXXFLAGS, *B.FILE_FLAGS.get(src, []), *flags, "-c", os.path.join(B.CSRC, src), "-o", obj], check=True)
-objs = [os.path.join(B.BUILD, f) for f in sorted(os.listdir(B.BUILD))
-        if f.endswith(".o") and f != src.replace(".hip", ".o")]
+# one object per present source (a tree built before a source was renamed still holds its old .o)
+objs = [os.path.join(B.BUILD, os.path.basename(s).replace(".hip", ".o")) for s in B._sources()
+        if os.path.basename(s) != src]
 subprocess.run([B.HIPCC, f"--offload-arch={B.ARCH}", "-shared", "-fPIC", "-o", os.path.join(out_dir, name + ".so"),
                 obj, *objs], check=True)
 os.remove(obj)
