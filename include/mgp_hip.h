@@ -77,7 +77,13 @@ const char* mgp_status_string(int status);
  * Replaces Kmn = self.kernel.K(self.X_data.Z, Xnew) (models.py:139; GPflow
  * SquaredExponential.K -> square_distance + K_r2).  n_ls = 1 (isotropic) or D
  * (ARD).  X: [N, D] (ld ldx), Z: [M, D] (ld ldz), Kuf: [M, N] (ld ldk % 4 == 0).
- * D <= 32 (D > 32: MGP_ERR_UNSUPPORTED). */
+ * D <= 32 (D > 32: MGP_ERR_UNSUPPORTED).
+ * Translation: every RBF entry (this one, mgp_rbf_kuu, mgp_rbf_kuf_x6 / _f16, the Kuf side
+ * job of mgp_kuu_potrf_trtri_kuf and the Knn of mgp_full_cov_conditional) differences the
+ * raw coordinates from a point taken from the data (Z[0], X[0], a centre of Z's rows) where
+ * they are loaded, before any scaling or product, so K(Z + c, X + c) = K(Z, X): the float32
+ * error depends on the data's spread in lengthscale units, not on its offset.  A Kuf image's
+ * trailer holds that centre's offset from Z[0] in its floats [32, 64). */
 int mgp_rbf_kuf(const float* X, int64_t ldx, const float* Z, int64_t ldz, int64_t N, int64_t M,
                 int32_t D, const float* variance, const float* lengthscales, int32_t n_ls,
                 float* Kuf, int64_t ldk, mgp_stream_t stream);

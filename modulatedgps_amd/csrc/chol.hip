@@ -925,6 +925,16 @@ __global__ __launch_bounds__(kCholThreads) void chol_prep(CholArgs a) {
       if (gr < a.M && gc < a.M) prep_store(dst + gr * a.ldl + gc, 0.f);
     }
   }
+  // the Kuf side job's reference point (kuf_image.hpp), into the image's trailer, by a
+  // workgroup that only fills zeros (tile (0, 1): there are step launches, nb >= 2)
+  if (blockIdx.x == 2 && !a.A && a.kx && threadIdx.x < kKufCentreFloats) {
+    float* kb = a.kbound[0];
+#pragma unroll
+    for (int i = 1; i < kMaxBatch; ++i)
+      if (b == i) kb = a.kbound[i];
+    const int d = threadIdx.x;
+    kb[kKufCentreFloats + d] = d < a.D ? kuf_centre_offset(Zb, a.ldz, a.M, d) : 0.f;
+  }
 }
 
 // chol_prep for a float64 input: batch entry b is the symmetric matrix Ad + b strideAd
@@ -1066,10 +1076,10 @@ __device__ __forceinline__ void kuf_side_blocks(const CholArgs& a, int w, int64_
     const KernargCholArgs& ag = *(const KernargCholArgs*)(
         (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr() + kStepArgsOffset);
     const KufImageArgs ka = {a.kx, a.kldx, ag.Z[b], a.ldz, a.kN, a.M, a.D, ag.var[b], ag.ls[b], ag.n_ls[b],
-                             a.knmk, a.krow_blocks, ag.kfr[b], ag.kbound[b]};
+                             a.knmk, a.krow_blocks, ag.kfr[b], ag.kbound[b], ag.kbound[b] + kKufCentreFloats};
     const int64_t bid = item - b * a.kblocks;
-    if (a.kf16) kuf_image_block<DM, true, MGP_KUF_SIDE_POLICY>(ka, bid, t, active, lds);
-    else kuf_image_block<DM, false, MGP_KUF_SIDE_POLICY>(ka, bid, t, active, lds);
+    if (a.kf16) kuf_image_block<DM, true, MGP_KUF_SIDE_POLICY, true>(ka, bid, t, active, lds);
+    else kuf_image_block<DM, false, MGP_KUF_SIDE_POLICY, true>(ka, bid, t, active, lds);
   }
 }
 

@@ -28,7 +28,8 @@ constexpr int kFragBytes = 1024;
 constexpr int64_t x6_mp(int64_t M) { return (M + kX6BM - 1) / kX6BM * kX6BM; }
 constexpr int64_t x6_np(int64_t N) { return (N + kX6BN - 1) / kX6BN * kX6BN; }
 
-// Image = fragment planes + a 256-byte trailer whose first float is the
+// Image = fragment planes + a 256-byte trailer (a Kuf image keeps its reference point's
+// offset in floats [32, 64), kuf_image.hpp) whose first float is the
 // split-f16 scale bound (unused by split-bf16 images).
 constexpr size_t kTrailer = 256;
 constexpr size_t lower_planes(int64_t M, int32_t K) {

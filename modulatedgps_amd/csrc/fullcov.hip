@@ -186,7 +186,9 @@ __global__ __launch_bounds__(kFcNT) void fullcov_syrk_kernel(
   floatx16 base[2][2];
   FcGemm<false>::run(base, lds, A, lda, N, i0, A, lda, N, j0, M, 0, M);
   {
-    // x / lengthscale of the tile's rows (sXi) and columns (sXj), zero beyond N
+    // (x - X[0]) / lengthscale of the tile's rows (sXi) and columns (sXj), zero beyond N:
+    // relative to the first point before the scaling, so Knn does not depend on where the
+    // data sits (the rounding of a scaled coordinate grows with the spread about X[0])
     float* sXi = lds;
     float* sXj = lds + kFcBT * kFcXld;
     for (int idx = threadIdx.x; idx < 2 * kFcBT * D; idx += kFcNT) {
@@ -194,7 +196,7 @@ __global__ __launch_bounds__(kFcNT) void fullcov_syrk_kernel(
       const int p = rem / D, d = rem % D;
       const int64_t g = (side ? j0 : i0) + p;
       const float ls = lengthscales[n_ls == 1 ? 0 : d];
-      (side ? sXj : sXi)[p * kFcXld + d] = g < N ? X[g * ldx + d] / ls : 0.f;
+      (side ? sXj : sXi)[p * kFcXld + d] = g < N ? (X[g * ldx + d] - X[d]) / ls : 0.f;
     }
     __syncthreads();
     const float var = variance[0];

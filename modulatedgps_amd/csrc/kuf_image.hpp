@@ -5,7 +5,34 @@
 // Reference: MixtureGPs/models.py:139 (self.kernel.K(Z, Xnew)); GPflow 2.7
 // SquaredExponential.K_r2(r2) = var * exp(-0.5 r2), r2 = square_distance(X / l, Z / l).
 //
-// r2 = |z'|^2 + |x'|^2 - 2 z'.x' (scaled inputs, the expanded form GPflow's
+// Numerics: z' and x' are the inputs RELATIVE TO A REFERENCE POINT OF THE LAYER, scaled:
+// z' = (z - ref) c, x' = (x - ref) c, c_d = sqrt(0.5 log2 e) / l_d, with
+// ref = Z[0] + mean_i (Z[i M / 32] - Z[0]), i < 32 (a cheap centre of the inducing points:
+// Z[0] alone doubles |z'|^2 + |x'|^2 on centred data).  Both subtractions, of Z[0] and of
+// the offset from it, are done on the raw coordinates where they are loaded (block
+// prologue), before the multiply by c.  The three terms of the expanded form below
+// cancel, so the absolute f32 error of r2 is a few eps32 (|z'|^2 + |x'|^2): with the
+// reference point taken out that is the squared spread of the data about it in
+// lengthscale units, not the squared distance from the origin, and
+// K(Z + c, X + c) = K(Z, X) -- bit for bit whenever the shifted coordinates and their
+// differences are exact in float32 (only differences of raw coordinates are formed).
+// The offset from Z[0] (kuf_centre_offset, a fixed summation order: the same bits wherever
+// it is computed) lives in floats [32, 64) of the image's trailer.  The stand-alone
+// launch's blocks each compute it (block 0 stores it); for K3's side job the prep launch
+// computes it once per layer and the step launches' blocks read it (PRE), because the
+// 31 row loads inlined into the step kernel cost that kernel 60 to 330 more spilled
+// SGPRs and K3 a fifth of its time.  Either way the images are byte-identical.
+// Data that spans tens of lengthscales is still out of reach of the expanded form at
+// f32 class (inputs over 20 lengthscales: ~1e-6 normwise).
+// D = 1 (DMAX = 1: time series, where the inputs span the most lengthscales) does not
+// use the expanded form: rows carry (z', 1), columns (1, -x'), the one MFMA product is
+// the difference z' - x' (products by 1 exact, one rounding) and each lane squares its
+// accumulators -- the direct form sum_d (z'_d - x'_d)^2, never negative, whose error is
+// that of the scaled coordinates only (eps32 |z' - x'| (|z'| + |x'|)).  That error is
+// linear in the distance from the reference point, so there z' and x' are taken from Z[0]
+// itself: the arithmetic of rbf.hip's rbf_kernel.
+//
+// r2 = |z'|^2 + |x'|^2 - 2 z'.x' (the expanded form GPflow's
 // square_distance uses) is ONE [32 x (D + 2)] x [(D + 2) x 32] product on
 // v_mfma_f32_32x32x2_f32 (exact f32 products): rows of Z carry (z', |z'|^2, 1),
 // columns of X carry (-2 x', 1, |x'|^2).  The accumulator of that MFMA holds
@@ -36,12 +63,30 @@ struct KufImageArgs {
   const float* variance; const float* ls; int n_ls;
   int nmk, row_blocks;
   bf16x8* Kfr; float* bound;
+  float* centre;   // the image trailer's floats [32, 64): the reference point's offset from Z[0]
 };
 
-// LDS floats a group needs: zs [128][DP] + cs [2 KS]
+// LDS floats a group needs: zs [128][DP] + cs [2 KS] + rf [2][2 KS]
 template <int DMAX>
 constexpr int kuf_block_lds_floats() {
-  return 128 * (2 * ((DMAX + 1) / 2 + 1) + 1) + 2 * ((DMAX + 1) / 2);
+  return 128 * (2 * ((DMAX + 1) / 2 + 1) + 1) + 6 * ((DMAX + 1) / 2);
+}
+
+// Rows of Z whose mean places the reference point (rows i M / kKufCentre, i = 0 ..)
+constexpr int kKufCentre = 32;
+constexpr int kKufCentreFloats = 32;   // floats [32, 64) of the image's trailer hold the offset
+// The reference point's offset from Z[0] in dimension d: the mean of Z[i M / 32][d] - Z[0][d],
+// i < 32, summed in this order wherever it is computed (the stand-alone launch's blocks,
+// K3's prep launch for the side job): the same bits.  Only differences of raw coordinates
+// are formed, so the offset does not move with the data.
+__device__ __forceinline__ float kuf_centre_offset(const float* __restrict__ Z, int64_t ldz, int64_t M, int d) {
+  const float z0 = Z[d];
+  float dl = 0.f;
+  // (all 31 loads in flight: the block waits for them before its first barrier; eight at a
+  // time kept the stand-alone kernel at 50 VGPRs but cost it 5 us of 47)
+#pragma unroll
+  for (int i = 1; i < kKufCentre; ++i) dl += Z[(i * M / kKufCentre) * ldz + d] - z0;
+  return dl * (1.f / kKufCentre);
 }
 
 // Stores of the image fragments (16 B per lane): POL 0 plain, 1 non-temporal (streaming:
@@ -87,41 +132,78 @@ __device__ __forceinline__ void store_fragment(bf16x8* __restrict__ dst, const f
 // __syncthreads(); a group with nothing to do passes active = false (it joins the
 // barriers, loads and stores nothing).  lds: kuf_block_lds_floats<DMAX>() floats of
 // this group's own.
-template <int DMAX, bool F16, int POL = 0>
+template <int DMAX, bool F16, int POL = 0, bool PRE = false>
 __device__ __forceinline__ void kuf_image_block(const KufImageArgs& a, int64_t bid, int t, bool active,
                                                 float* __restrict__ lds) {
   constexpr int KS = (DMAX + 1) / 2;     // MFMA k-steps over the dims (2 each) ...
   constexpr int KA = KS + 1;             // ... + one for the (|z'|^2, 1) x (1, |x'|^2) terms
+  constexpr int KM = DMAX == 1 ? 1 : KA; // MFMAs per tile (D = 1: the one difference product)
   constexpr int DP = 2 * KA + 1;         // LDS row pitch (odd: spreads banks)
   float* zs = lds;
   float* cs = lds + 128 * DP;
+  float* rf = cs + 2 * KS;               // reference point: rf[d] = Z[0][d], rf[2 KS + d] = offset from it
   const int lane = t & 63, w = t >> 6, h = lane >> 5, c32 = lane & 31;
   const int64_t rb = bid % a.row_blocks, cg = bid / a.row_blocks;
   const int64_t nb = cg * 4 + w;
   const int64_t n = 32 * nb + c32;
   const int64_t m0 = 128 * rb;
   const float kHalfLog2e = 0.8493218002880191f;  // sqrt(0.5 * log2(e))
-  if (active && t < 2 * KS) cs[t] = (t < a.D) ? kHalfLog2e / a.ls[a.n_ls == 1 ? 0 : t] : 0.f;
+  // this thread's raw coordinates, issued before the scale and the reference point are
+  // fetched (their latency overlaps; the arithmetic waits for the barrier): KS elements
+  // of the block's Z rows and the KS dims of its column of X this lane half carries
+  float zraw[KS], xraw[KS];
+#pragma unroll
+  for (int q = 0; q < KS; ++q) {
+    const int i = t + 256 * q, r = i / (2 * KS), d = i % (2 * KS), dx = DMAX == 1 ? 0 : 2 * q + h;
+    zraw[q] = (active && m0 + r < a.M && d < a.D) ? a.Z[(m0 + r) * a.ldz + d] : 0.f;
+    xraw[q] = (active && n < a.N && dx < a.D) ? a.X[n * a.ldx + dx] : 0.f;
+  }
+  if (active && t < 2 * KS) {
+    cs[t] = (t < a.D) ? kHalfLog2e / a.ls[a.n_ls == 1 ? 0 : t] : 0.f;
+    // the reference point Z[0] + offset (kuf_centre_offset): read from the image's trailer
+    // where a launch before this one has put it (PRE: K3's side job), computed here otherwise
+    float z0 = 0.f, dl = 0.f;
+    if (t < a.D) {
+      z0 = a.Z[t];
+      dl = PRE ? a.centre[t] : kuf_centre_offset(a.Z, a.ldz, a.M, t);
+    }
+    rf[t] = z0;
+    rf[2 * KS + t] = dl;
+    if (!PRE && bid == 0) a.centre[t] = dl;
+  }
+  if (!PRE && active && bid == 0 && t >= 2 * KS && t < kKufCentreFloats) a.centre[t] = 0.f;
   __syncthreads();
   float xk[KA], xx = 0.f;
   if (active) {
-    for (int i = t; i < 128 * 2 * KS; i += 256) {
-      const int r = i / (2 * KS), d = i % (2 * KS);
-      const int64_t m = m0 + r;
-      zs[r * DP + d] = (m < a.M && d < a.D) ? a.Z[m * a.ldz + d] * cs[d] : 0.f;
-    }
 #pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int d = 2 * s + h;
-      const float xd = (n < a.N && d < a.D) ? a.X[n * a.ldx + d] * cs[d] : 0.f;
-      xx = fmaf(xd, xd, xx);
-      xk[s] = -2.f * xd;
+    for (int q = 0; q < KS; ++q) {
+      const int i = t + 256 * q, r = i / (2 * KS), d = i % (2 * KS);
+      const int64_t m = m0 + r;
+      if constexpr (DMAX == 1)   // rows carry (z', 1), z' from Z[0]
+        zs[r * DP + d] = d ? 1.f : (m < a.M) ? (zraw[q] - rf[0]) * cs[0] : 0.f;
+      else
+        zs[r * DP + d] = (m < a.M && d < a.D) ? ((zraw[q] - rf[d]) - rf[2 * KS + d]) * cs[d] : 0.f;
     }
+    if constexpr (DMAX == 1) {
+      // columns carry (1, -x'): the product is the difference z' - x' itself
+      const float x0 = (n < a.N) ? (xraw[0] - rf[0]) * cs[0] : 0.f;
+      xk[0] = h ? -x0 : 1.f;
+    } else {
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        const int d = 2 * s + h;
+        const float xd = (n < a.N && d < a.D) ? ((xraw[s] - rf[d]) - rf[2 * KS + d]) * cs[d] : 0.f;
+        xx = fmaf(xd, xd, xx);
+        xk[s] = -2.f * xd;
+      }
+    }
+  } else if constexpr (DMAX == 1) {
+    xk[0] = 0.f;
   }
   xx += __shfl_xor(xx, 32, 64);  // the two lane halves hold the even / odd dims
   xk[KS] = h ? xx : 1.f;         // k = 2 KS: |z'|^2 * 1, k = 2 KS + 1: 1 * |x'|^2
   __syncthreads();
-  if (active && t < 128) {
+  if (DMAX > 1 && active && t < 128) {
     float s2 = 0.f;
 #pragma unroll
     for (int d = 0; d < 2 * KS; ++d) s2 = fmaf(zs[t * DP + d], zs[t * DP + d], s2);
@@ -147,7 +229,11 @@ __device__ __forceinline__ void kuf_image_block(const KufImageArgs& a, int64_t b
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[e] = 0.f;
 #pragma unroll
-      for (int s = 0; s < KA; ++s) acc = mfma32x32x2(zs[(32 * i + c32) * DP + 2 * s + h], xk[s], acc);
+      for (int s = 0; s < KM; ++s) acc = mfma32x32x2(zs[(32 * i + c32) * DP + 2 * s + h], xk[s], acc);
+      if constexpr (DMAX == 1) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] *= acc[e];
+      }
       const int64_t mb = (m0 >> 5) + i;
 #pragma unroll
       for (int half = 0; half < 2; ++half) {

@@ -15,6 +15,11 @@
 // Numerics: direct-difference form sum_d (z_d - x_d)^2 * c_d^2 (exact symmetric,
 // never negative) instead of GPflow's |a|^2 + |b|^2 - 2ab expansion; the
 // exp(-0.5 r2) is evaluated as exp2(-r2') with c_d = sqrt(0.5 log2 e) / l_d.
+// Both operands are taken relative to the first row of Z before they are scaled
+// (z_d - Z[0]_d, x_d - Z[0]_d, subtracted where the coordinates are loaded), so the
+// rounding of a scaled coordinate grows with the data's spread about that point, not
+// with its distance from the origin: K(Z + c, X + c) = K(Z, X), bit for bit whenever
+// the shifted coordinates and their differences are exact in float32.
 #include <type_traits>
 
 #include "kuf_image.hpp"
@@ -44,14 +49,14 @@ __global__ __launch_bounds__(kRbfThreads) void rbf_kernel(
   for (int i = t; i < kRbfTileM * DMAX; i += kRbfThreads) {
     const int r = i / DMAX, d = i % DMAX;
     const int64_t m = m0 + r;
-    zs[r][d] = (m < M && d < D) ? Z[m * ldz + d] * cs[d] : 0.f;
+    zs[r][d] = (m < M && d < D) ? (Z[m * ldz + d] - Z[d]) * cs[d] : 0.f;
   }
   float xs[kRbfCols][DMAX];
 #pragma unroll
   for (int j = 0; j < kRbfCols; ++j) {
     const int64_t n = n0 + j;
 #pragma unroll
-    for (int d = 0; d < DMAX; ++d) xs[j][d] = (n < N && d < D) ? X[n * ldx + d] * cs[d] : 0.f;
+    for (int d = 0; d < DMAX; ++d) xs[j][d] = (n < N && d < D) ? (X[n * ldx + d] - Z[d]) * cs[d] : 0.f;
   }
   const float var = variance[0];
   __syncthreads();
@@ -92,7 +97,8 @@ __global__ __launch_bounds__(kRbfThreads) void rbf_kuf_x6_kernel(
     int64_t M, int D, const float* __restrict__ variance, const float* __restrict__ ls, int n_ls, int nmk,
     bf16x8* __restrict__ Kfr, float* __restrict__ bound, int row_blocks) {
   __shared__ float lds[kuf_block_lds_floats<DMAX>()];
-  const KufImageArgs a = {X, ldx, Z, ldz, N, M, D, variance, ls, n_ls, nmk, row_blocks, Kfr, bound};
+  const KufImageArgs a = {X, ldx, Z, ldz, N, M, D, variance, ls, n_ls, nmk, row_blocks, Kfr, F16 ? bound : nullptr,
+                          bound + kKufCentreFloats};
   kuf_image_block<DMAX, F16>(a, blockIdx.x, threadIdx.x, true, lds);
 }
 
@@ -449,7 +455,7 @@ static int rbf_kuf_image(const float* X, int64_t ldx, const float* Z, int64_t ld
                          variance, lengthscales, n_ls, nmk, (bf16x8*)Kfr, bound, row_blocks);                      \
     else                                                                                               \
       hipLaunchKernelGGL((rbf_kuf_x6_kernel<DM, false>), grid, block, 0, s, X, ldx, Z, ldz, N, M, D,   \
-                         variance, lengthscales, n_ls, nmk, (bf16x8*)Kfr, nullptr, row_blocks);                    \
+                         variance, lengthscales, n_ls, nmk, (bf16x8*)Kfr, bound, row_blocks);                    \
     return launch_status();                                                                            \
   }
   MGP_RBF_X6_CASE(1)

@@ -129,16 +129,22 @@ def test_elbo_and_grad_c3_full(device):
     _check_elbo_and_grad(device, 65536, 1024, 8, 8, 1.0, 25, False)
 
 
-def _check_elbo_and_grad(device, N, M, K, D, ls, S, modified, floor=None, floors=None, factor=1.5):
+def _check_elbo_and_grad(device, N, M, K, D, ls, S, modified, floor=None, floors=None, factor=1.5, problem=None,
+                         device_problem=None):
+    """problem: (X, Y, p) for the oracle instead of the synthetic problem of these sizes;
+    device_problem: (X, p) the device model is built from and evaluated at where that is not
+    the oracle's (the same problem translated: tests/test_gpu_translation.py).  Returns the
+    device's ELBO and gradients."""
     floor = FLOOR if floor is None else floor
     floors = floors or {}
-    X, Y, p = R.synthetic_problem(N, M, K, D, ls, state="perturbed", S=S)
+    X, Y, p = problem if problem is not None else R.synthetic_problem(N, M, K, D, ls, state="perturbed", S=S)
+    Xm, pm = device_problem if device_problem is not None else (X, p)
     a_var = np.linspace(0.3, 0.9, K)[None, :] if modified else None
     z, u = R.explicit_noise(S, N, K, seed=5)
     e_ref, g_ref = _oracle(X, Y, p, z, u, a_var)
     _, g_f32 = _oracle(X, Y, p, z, u, a_var, dtype=torch.float32)
-    model = _model(p, device, a_var)
-    Xd = torch.as_tensor(X, dtype=torch.float32, device=device)
+    model = _model(pm, device, a_var)
+    Xd = torch.as_tensor(Xm, dtype=torch.float32, device=device)
     e, grads = model.elbo_and_grad(Xd, Y, noise=dev_noise(z, u, device))
     assert float(e.cpu()) == pytest.approx(e_ref, rel=1e-4)
     names = [n for n, _, _ in model.trainable_parameters()]
@@ -155,6 +161,7 @@ def _check_elbo_and_grad(device, N, M, K, D, ls, S, modified, floor=None, floors
     print({k: f"{v:.1e}/{errs32[k]:.1e}" for k, v in errs.items()})
     for n, err in errs.items():
         assert err < max(floors.get(n, floor), factor * errs32[n]), (n, err, errs32[n])
+    return e, grads
 
 
 def test_adam_step(device):
