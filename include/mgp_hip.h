@@ -105,7 +105,9 @@ int mgp_rbf_kuu(const float* Z, int64_t ldz, int64_t M, int32_t D, const float* 
  * triangular_solve.  `batch` matrices at element strides strideA / strideL
  * (the two SVGP layers of one ELBO share every launch).  info[b] = 0, or the
  * 1-based column of the first non-positive pivot (LAPACK potrf convention);
- * the factor then carries NaN.  L may be NULL.  lda, ldl % 4 == 0. */
+ * the factor then carries NaN.  L may be NULL.  ldl (and strideL when batch > 1) % 4 == 0
+ * and L, LinvT 16-B aligned (MGP_ERR_ALIGN: their tiles are written with 16-B stores); A is
+ * read by elements, any lda >= M and strideA >= M lda. */
 size_t mgp_chol_workspace_bytes(int64_t M, int32_t batch);
 int mgp_potrf_trtri(const float* A, int64_t lda, int64_t strideA, int64_t M, int32_t batch,
                     float* L, float* LinvT, int64_t ldl, int64_t strideL, int32_t* info,
@@ -410,7 +412,9 @@ int mgp_full_cov_conditional(const float* X, int64_t ldx, int64_t N, int32_t D, 
 /* ---------------------------------------------------------------- backward of K1-K5
  * Gram products over the data dimension (float32 MFMA, deterministic split-K):
  *   out[i][j] = alpha * sum_n X[i][n] Y[j][n]   (tri != 0: j <= i only, zeros above)
- * X [MI][ldx], Y [MJ][ldy]; workspace mgp_gram_workspace_bytes(MI, MJ, N, tri). */
+ * X [MI][ldx], Y [MJ][ldy]; workspace mgp_gram_workspace_bytes(MI, MJ, N, tri).
+ * ldx, ldy % 4 == 0 and X, Y 16-B aligned (MGP_ERR_ALIGN), except where MJ <= 16 and
+ * tri == 0: that path reads by elements.  Any ldo >= MJ. */
 size_t mgp_gram_workspace_bytes(int64_t MI, int64_t MJ, int64_t N, int32_t tri);
 int mgp_gram(const float* X, int64_t ldx, int64_t MI, const float* Y, int64_t ldy, int64_t MJ, int64_t N,
              float alpha, int32_t tri, float* out, int64_t ldo, void* workspace, size_t workspace_bytes,
@@ -470,7 +474,11 @@ int mgp_gram_f16_rows(const void* ximg, size_t ximg_bytes, int64_t MI, const flo
  * that scales with N runs on the split-bf16 x6 path (f32 accuracy), g_q_mu on
  * the f32 MFMA.  Workspace: mgp_conditional_backward_workspace_bytes.  K <= 16
  * (K > 16: MGP_ERR_UNSUPPORTED) for every mgp_conditional_backward_* entry and for
- * mgp_conditional_backward_prep_f16c. */
+ * mgp_conditional_backward_prep_f16c.  lda, ldk (and ldg when K > 1) % 4 == 0 and A, Gv,
+ * g_Kuf 16-B aligned (MGP_ERR_ALIGN, before anything is launched: they are operands and
+ * weights of the grams over N); every other leading dimension and stride is free: ldqs,
+ * strideq, ldl, ldgq, ldgs, strideg, ldgl, and ldq (a q_mu with ldq % 4 != 0 or K % 4 != 0
+ * is read by elements). */
 size_t mgp_conditional_backward_workspace_bytes(int64_t M, int64_t N, int32_t K);
 int mgp_conditional_backward_x6(const void* Afr, size_t afr_bytes, const float* A, int64_t lda,
                                 const float* q_sqrt, int64_t ldqs,
@@ -586,7 +594,9 @@ int mgp_rbf_backward_batch(int32_t batch, const float* X, int64_t ldx, int64_t N
  * Whitened Gaussian KL (GPflow gauss_kl(q_mu, q_sqrt, K=None), reached through
  * SVGP.prior_kl at models.py:79):
  *   kl = 0.5 * (sum q_mu^2 - M*K - sum_k sum_m log(L_k[m,m]^2) + sum_k ||tril L_k||_F^2)
- * Written as one double to kl_out (device).  Workspace: mgp_kl_workspace_bytes. */
+ * Written as one double to kl_out (device).  Workspace: mgp_kl_workspace_bytes.
+ * ldqs and strideq % 4 == 0 and q_sqrt 16-B aligned (MGP_ERR_ALIGN: its rows are read as
+ * float4); any ldq >= K. */
 size_t mgp_kl_workspace_bytes(int64_t M, int32_t K);
 int mgp_gauss_kl_white(const float* q_mu, int64_t ldq, const float* q_sqrt, int64_t ldqs,
                        int64_t strideq, int64_t M, int32_t K, double* kl_out, void* workspace,

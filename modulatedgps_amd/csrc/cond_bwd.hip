@@ -1319,6 +1319,11 @@ static int conditional_backward(
   if (!g_var) return -29;
   if (!workspace || workspace_bytes < mgp_conditional_backward_workspace_bytes(M, N, K)) return MGP_ERR_WORKSPACE;
   if (!aligned16(workspace) || !aligned16(Afr)) return MGP_ERR_ALIGN;
+  // A and g_Kuf are operands of the grams over N (float4 rows) and Gv their weights, one
+  // expert every ldg floats: refused here, before anything is launched, not by the grams
+  // (with their own argument numbers, and g_Kuf already written)
+  if (lda % 4 || ldk % 4 || (K > 1 && ldg % 4) || !aligned16(A) || !aligned16(Gv) || !aligned16(g_Kuf))
+    return MGP_ERR_ALIGN;
   const size_t img = mgp_x6_cols_bytes(M, N);
   if (img >= ((size_t)1 << 32) || (size_t)M * ((N + 3) / 4 * 4) * 4 >= ((size_t)1 << 32)) return MGP_ERR_UNSUPPORTED;
   // the S_k / L_k image is addressed through one 32-bit buffer resource by the gA kernels

@@ -870,6 +870,8 @@ extern "C" int mgp_gram(const float* X, int64_t ldx, int64_t MI, const float* Y,
   if (!out) return -10;
   if (ldo < MJ) return -11;
   if (MI == 0 || MJ == 0) return MGP_OK;
+  // the 128 x 128 tiles load X and Y as float4 (gload4); the narrow path reads by elements
+  if (!gram_narrow(MJ, tri) && (ldx % 4 || ldy % 4 || !aligned16(X) || !aligned16(Y))) return MGP_ERR_ALIGN;
   if (!workspace || workspace_bytes < mgp_gram_workspace_bytes(MI, MJ, N, tri)) return MGP_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   if (gram_narrow(MJ, tri)) {

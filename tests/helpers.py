@@ -38,6 +38,83 @@ def build_model(p, device, seed=0):
     return SMGP(lik, layers[0], layers[1], K=K, num_samples=p.S, num_data=p.num_data, seed=seed)
 
 
+def unequal_problem(N, Mf, Ma, K, D, ls_f, ls_a, S, seed=0):
+    """The synthetic problem with layers that differ: pred_layer keeps Mf inducing points
+    and lengthscales ls_f, assign_layer Ma and ls_a (a scalar: isotropic; D values: ARD).
+    Drawn at max(Mf, Ma) and cut per layer (a leading block of tril(q_sqrt) is lower
+    triangular with the same positive diagonal).  Returns (X, Y, SMGPParams)."""
+    X, Y, p = R.synthetic_problem(N, max(Mf, Ma), K, D, 1.0, state="perturbed", S=S, seed=seed)
+    for L, M, ls in ((p.pred, Mf, ls_f), (p.assign, Ma, ls_a)):
+        L["Z"] = L["Z"][:M].copy()
+        L["q_mu"] = L["q_mu"][:M].copy()
+        L["q_sqrt"] = L["q_sqrt"][:, :M, :M].copy()
+        L["lengthscales"] = float(ls) if np.ndim(ls) == 0 else np.asarray(ls, np.float64).reshape(D).copy()
+    return X, Y, p
+
+
+# (N, Mf, Ma, K, D, ls_f, ls_a, S): models whose two layers differ in M and / or in the
+# kind of lengthscale (tests/test_gpu_unequal_layers.py, tests/test_oracle.py)
+UNEQUAL_CASES = {
+    "a": (301, 40, 25, 3, 2, [0.3, 0.5], 0.4, 5),                      # both M <= 64; pred ARD
+    "b": (777, 130, 64, 4, 3, 0.6, [0.5, 0.6, 0.9], 3),                # two row tiles / one; assign ARD
+    "c": (777, 64, 130, 4, 3, [0.5, 0.6, 0.9], 0.6, 3),                # b with the larger layer second
+    "d": (513, 33, 160, 5, 8, np.linspace(1.5, 2.5, 8), 2.0, 2),       # K no multiple of 4
+    "e": (515, 129, 128, 8, 8, 2.0, np.linspace(1.5, 2.5, 8), 2),      # stats tile counts differ by one
+    "f": (130, 1, 17, 2, 2, 0.8, 0.8, 2),                              # degenerate M = 1 layer
+    "g": (301, 40, 40, 3, 2, [0.3, 0.5], 0.4, 5),                      # equal M, mixed lengthscale counts
+}
+
+
+def round4(n):
+    return (n + 3) // 4 * 4
+
+
+def poison_like(poison, shape, device):
+    """A float32 tensor of the padding pattern: "nan", or "big" = 3e38 with alternating sign."""
+    if poison == "nan":
+        return torch.full(shape, float("nan"), dtype=torch.float32, device=device)
+    n = int(np.prod(shape))
+    sign = 1.0 - 2.0 * (torch.arange(n, device=device) % 2).float()
+    return (3e38 * sign).reshape(shape)
+
+
+def wide(values, ld, poison, device, batch_stride=None):
+    """A float32 device view of values' shape over storage of row length ld (floats).  Every
+    element outside the view holds the poison pattern: the padding columns and, for 3-D
+    values, the gap between batch entries (batch_stride > rows * ld).  A 1-D values is one
+    row.  An output buffer is wide(zeros, ld, "nan", ...) filled with a sentinel by the caller."""
+    v = torch.as_tensor(np.asarray(values), dtype=torch.float32)
+    if v.dim() == 1:
+        v = v[None]
+    rows, cols = v.shape[-2:]
+    assert ld >= cols
+    if v.dim() == 2:
+        store = poison_like(poison, (rows * ld,), device)
+        view = store.as_strided((rows, cols), (ld, 1))
+    else:
+        bs = rows * ld if batch_stride is None else batch_stride
+        assert bs >= rows * ld
+        store = poison_like(poison, (v.shape[0] * bs,), device)
+        view = store.as_strided((v.shape[0], rows, cols), (bs, ld, 1))
+    view.copy_(v.to(device))
+    return view
+
+
+def _storage_bits(view):
+    n = view.untyped_storage().nbytes() // 4
+    return view.as_strided((n,), (1,), 0).view(torch.int32)
+
+
+def padding_intact(view, poison):
+    """Every storage element outside the view still holds the poison pattern, compared as
+    bit patterns (a NaN sentinel compares equal to itself)."""
+    bits = _storage_bits(view).clone()
+    want = poison_like(poison, (bits.numel(),), view.device).view(torch.int32).clone()
+    inside = torch.zeros(bits.numel(), dtype=torch.bool, device=view.device)
+    inside.as_strided(view.shape, view.stride(), view.storage_offset()).fill_(True)
+    return bool(torch.equal(bits[~inside], want[~inside]))
+
+
 def normwise(a, b):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)

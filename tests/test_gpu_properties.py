@@ -75,6 +75,33 @@ def test_elbo_and_conditionals_random_shapes(device, shape):
     assert close(pa, R.predict_assign(Xt.astype(np.float32).astype(np.float64), p)), (shape, "predict_assign")
 
 
+@st.composite
+def unequal_shapes(draw):
+    """shapes() plus a second, independent M in the same range and one ARD flag per layer."""
+    N, M, K, D, S, ls = draw(shapes())
+    m_max = min(N, 24 if D == 1 else (96 if D == 2 else 300))
+    Ma = draw(st.integers(min_value=1, max_value=m_max))
+    return N, M, Ma, K, D, S, ls, draw(st.booleans()), draw(st.booleans())
+
+
+@settings(max_examples=12, deadline=None, derandomize=True, database=None,
+          suppress_health_check=[HealthCheck.function_scoped_fixture, HealthCheck.too_slow])
+@given(shape=unequal_shapes())
+def test_unequal_layers_random_shapes(device, shape):
+    """Layers that differ (tests/test_gpu_unequal_layers.py) at drawn shapes: each layer
+    its own M and its own kind of lengthscale (ARD: ls * linspace(0.8, 1.25, D)); the ELBO
+    and the four conditionals at the tolerances of test_elbo_and_conditionals_random_shapes."""
+    from tests.helpers import unequal_problem
+    from tests.test_gpu_unequal_layers import check_elbo_and_conditionals
+    N, Mf, Ma, K, D, S, ls, ard_f, ard_a = shape
+    print("unequal shape (N, Mf, Ma, K, D, S, ls, ard_f, ard_a):", shape, flush=True)
+    ard = ls * np.linspace(0.8, 1.25, D)
+    X, Y, p = unequal_problem(N, Mf, Ma, K, D, ard if ard_f else ls, ard if ard_a else ls, S)
+    z, u = R.explicit_noise(S, N, K, seed=7)
+    ref, parts = R.smgp_elbo(X, Y, p, z, u, return_parts=True)
+    check_elbo_and_conditionals(device, X, Y, p, z, u, ref, parts, tag=shape)
+
+
 @_SETTINGS
 @given(shape=shapes())
 def test_layer_batched_launches_match_per_layer(device, shape):

@@ -187,6 +187,31 @@ def test_grad_oracle_value_matches_cpu_oracle(modified):
     assert pred["q_sqrt"].grad is not None and torch.isfinite(pred["q_sqrt"].grad).all()
 
 
+@pytest.mark.parametrize("case", ["a", "d", "f"])
+def test_grad_oracle_value_matches_cpu_oracle_unequal_layers(case):
+    """The two oracles agree where the layers differ in M and in the kind of
+    lengthscale (tests/helpers.py unequal_problem; tests/test_gpu_unequal_layers.py
+    leans on both)."""
+    import torch
+    from oracle import grad_ref as G
+    from tests.helpers import UNEQUAL_CASES, unequal_problem
+    N, Mf, Ma, K, D, ls_f, ls_a, S = UNEQUAL_CASES[case]
+    X, Y, p = unequal_problem(N, Mf, Ma, K, D, ls_f, ls_a, S)
+    assert p.pred["Z"].shape == (Mf, D) and p.assign["Z"].shape == (Ma, D)
+    assert p.pred["q_sqrt"].shape == (K, Mf, Mf) and p.assign["q_mu"].shape == (Ma, K)
+    for L in (p.pred, p.assign):
+        for k in ("Z", "q_mu", "q_sqrt"):
+            L[k] = np.asarray(L[k]).astype(np.float32).astype(np.float64)
+    z, u = R.explicit_noise(S, N, K)
+    pred, assign, lik = G.params_from_oracle(p)
+    e = G.elbo(torch.tensor(X), torch.tensor(Y), pred, assign, lik, torch.tensor(z), torch.tensor(u), p.num_data)
+    p.lik_variance = lik.detach().numpy().reshape(1, -1)
+    for L, T in ((p.pred, pred), (p.assign, assign)):
+        L["variance"] = float(T["variance"].detach())
+        L["lengthscales"] = T["lengthscales"].detach().numpy()
+    assert float(e.detach()) == pytest.approx(R.smgp_elbo(X, Y, p, z, u), rel=1e-10)
+
+
 # ----------------------------------------------------------------------------- MultiClass
 def _phi(x):
     from scipy.special import erf
