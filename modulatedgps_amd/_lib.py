@@ -30,249 +30,62 @@ class MGPLinAlgError(MGPError):
     raised from base_conditional (MixtureGPs/models.py:141)."""
 
 
-c_f32p = ctypes.c_void_p
-c_i64 = ctypes.c_int64
-c_i32 = ctypes.c_int32
-c_u64 = ctypes.c_uint64
-c_size = ctypes.c_size_t
-c_ptr = ctypes.c_void_p
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
+            "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "float": ctypes.c_float,
+            "double": ctypes.c_double, "mgp_stream_t": ctypes.c_void_p}
 
-# name -> (restype, argtypes); must mirror include/mgp_hip.h
-SIGNATURES = {
-    "mgp_version": (ctypes.c_char_p, []),
-    "mgp_status_string": (ctypes.c_char_p, [ctypes.c_int]),
-    "mgp_rbf_kuf": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i32, c_ptr, c_ptr,
-                                   c_i32, c_ptr, c_i64, c_ptr]),
-    "mgp_rbf_kuu": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_i32, ctypes.c_float,
-                                   c_ptr, c_i64, c_ptr]),
-    "mgp_chol_workspace_bytes": (c_size, [c_i64, c_i32]),
-    "mgp_potrf_trtri": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_i64, c_i64,
-                                       c_ptr, c_ptr, c_size, c_ptr]),
-    "mgp_kuu_potrf_trtri": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_ptr,
-                                           ctypes.c_float, c_i32, c_ptr, c_ptr, c_i64, c_i64, c_ptr,
-                                           c_ptr, c_size, c_ptr]),
-    "mgp_kuu_potrf_trtri_ev": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_ptr,
-                                           ctypes.c_float, c_i32, c_ptr, c_ptr, c_i64, c_i64, c_ptr,
-                                           c_ptr, c_size, c_ptr, c_ptr]),
-    "mgp_kuu_potrf_trtri_ex": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_ptr,
-                                           ctypes.c_float, c_i32, c_ptr, c_ptr, c_i64, c_i64, c_ptr,
-                                           c_ptr, c_size, c_ptr, c_ptr, c_ptr]),
-    "mgp_kuu_potrf_trtri_kuf": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_ptr,
-                                            ctypes.c_float, c_i32, c_ptr, c_ptr, c_i64, c_i64, c_ptr,
-                                            c_ptr, c_size, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_size,
-                                            c_i32, c_ptr]),
-    "mgp_stats_tiles": (ctypes.c_int, [c_i64]),
-    "mgp_trsm_stats": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i64, c_i32,
-                                      c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
-    "mgp_expert_workspace_bytes": (c_size, [c_i64, c_i64, c_i32]),
-    "mgp_expert_conditional_f32": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr,
-                                                  c_i64, c_i64, c_i32, c_ptr, c_ptr, c_i64, c_ptr, c_size,
-                                                  c_ptr]),
-    # full_cov=True conditional (csrc/fullcov.hip)
-    "mgp_full_cov_workspace_bytes": (c_size, [c_i64, c_i64, c_i32]),
-    "mgp_full_cov_conditional": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_i32, c_ptr, c_i64,
-                                                c_ptr, c_i64, c_i64, c_i64, c_i32, c_ptr, c_i64, c_i64, c_ptr,
-                                                c_size, c_ptr]),
-    # the SURVEY §8(b) front (csrc/front.hip)
-    "mgp_workspace_bytes": (c_size, [c_i32, c_i64, c_i64, c_i32]),
-    "mgp_rbf_kuu_jitter": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_i32, ctypes.c_float,
-                                          c_ptr, c_i64, c_ptr]),
-    "mgp_potrf_lower": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
-    "mgp_trsm_lln": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_size, c_ptr]),
-    "mgp_expert_conditional": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64,
-                                              c_i64, c_i32, c_ptr, c_ptr, c_i64, c_ptr, c_size, c_ptr]),
-    "mgp_trsm_stats_x6": (ctypes.c_int, [c_ptr, c_size, c_ptr, c_size, c_i64, c_i64, c_ptr, c_i64, c_i32,
-                                         c_ptr, c_size, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
-    "mgp_kl_grad": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i32, ctypes.c_double, c_ptr,
-                                   c_i64, c_ptr, c_i64, c_i64, c_ptr]),
-    "mgp_adam_step": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_i32, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_i64,
-                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_i64,
-                                     ctypes.c_float, c_ptr]),
-    "mgp_adam_step_set": (ctypes.c_int, [c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
-                                         c_ptr, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                         c_i64, ctypes.c_float, c_ptr]),
-    "mgp_rbf_backward_workspace_bytes": (c_size, [c_i64, c_i64, c_i32]),
-    "mgp_rbf_backward": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_i32,
-                                        c_ptr, c_i64, c_i32, c_i32, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_size,
-                                        c_ptr]),
-    "mgp_rbf_backward_batch_workspace_bytes": (c_size, [c_i64, c_i64, c_i32]),
-    "mgp_rbf_backward_batch": (ctypes.c_int, [c_i32, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_i32, c_ptr, c_ptr,
-                                              c_i32, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_ptr,
-                                              c_ptr, c_size, c_ptr]),
-    "mgp_chol_backward_batch": (ctypes.c_int, [c_i32, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr,
-                                               c_i64, c_ptr, c_size, c_ptr]),
-    "mgp_chol_backward_workspace_bytes": (c_size, [c_i64]),
-    "mgp_chol_backward": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr,
-                                         c_size, c_ptr]),
-    "mgp_gram_workspace_bytes": (c_size, [c_i64, c_i64, c_i64, c_i32]),
-    "mgp_gram": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_i64, ctypes.c_float, c_i32, c_ptr,
-                                c_i64, c_ptr, c_size, c_ptr]),
-    "mgp_gram_x6_workspace_bytes": (c_size, [c_i64, c_i64, c_i64, c_i32, c_i32]),
-    "mgp_gram_x6": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i64, c_i64,
-                                   c_i32, ctypes.c_float, c_i32, c_ptr, c_i64, c_i64, c_ptr, c_size, c_ptr]),
-    "mgp_gram_f16": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i64, c_i64,
-                                    c_i32, ctypes.c_float, c_i32, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
-                                    c_size, c_ptr]),
-    "mgp_rows_f16_ksteps": (c_i64, [c_i64]),
-    "mgp_rows_f16_bytes": (c_size, [c_i64, c_i64]),
-    "mgp_split_rows_f16": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
-    "mgp_gram_f16_rows": (ctypes.c_int, [c_ptr, c_size, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_i32,
-                                         ctypes.c_float, c_i32, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
-                                         c_size, c_ptr]),
-    "mgp_conditional_backward_workspace_bytes": (c_size, [c_i64, c_i64, c_i32]),
-    "mgp_conditional_backward_x6": (ctypes.c_int, [c_ptr, c_size, c_ptr, c_i64, c_ptr, c_i64,
-                                                   c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64,
-                                                   c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_i64,
-                                                   c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
-    "mgp_conditional_backward_f16": (ctypes.c_int, [c_ptr, c_size, c_ptr, c_i64, c_ptr, c_i64,
-                                                   c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64,
-                                                   c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_i64,
-                                                   c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
-    "mgp_conditional_backward_f16x8": (ctypes.c_int, [c_ptr, c_size, c_ptr, c_i64, c_ptr, c_i64,
-                                                   c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64,
-                                                   c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_i64,
-                                                   c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
-    "mgp_conditional_backward_f16c": (ctypes.c_int, [c_ptr, c_size, c_ptr, c_i64, c_ptr, c_i64,
-                                                    c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64,
-                                                    c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_i64,
-                                                    c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr,
-                                                    c_size, c_ptr, c_ptr, c_ptr]),
-    "mgp_conditional_backward_prep_bytes": (c_size, [c_i64, c_i32]),
-    "mgp_conditional_backward_prep_f16c": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_size,
-                                                         c_ptr]),
-    "mgp_conditional_backward_f16c_prepped": (ctypes.c_int, [c_ptr, c_size, c_ptr, c_i64, c_ptr, c_i64,
-                                                            c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64,
-                                                            c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_i64,
-                                                            c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr,
-                                                            c_size, c_ptr, c_ptr, c_ptr, c_size, c_ptr, c_ptr]),
-    "mgp_c_images_bytes": (c_size, [c_i64, c_i64, c_i32]),
-    "mgp_colnorm_max": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i64, c_i32, c_ptr, c_ptr]),
-    "mgp_expert_conditional_f16c": (ctypes.c_int, [c_ptr, c_size, c_ptr, c_size, c_ptr, c_i64, c_ptr, c_i64,
-                                                   c_i64, c_i32, c_ptr, c_ptr, c_i64, c_ptr, c_size, c_ptr, c_size,
-                                                   c_ptr, c_ptr]),
-    "mgp_split_upper_x6": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_ptr, c_size, c_ptr]),
-    "mgp_rbf_kuf_x6": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_i32,
-                                      c_ptr, c_size, c_ptr]),
-    "mgp_x6_lower_bytes": (c_size, [c_i64, c_i32]),
-    "mgp_x6_cols_bytes": (c_size, [c_i64, c_i64]),
-    "mgp_split_lower_x6": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i64, c_i32, c_ptr, c_size, c_ptr]),
-    "mgp_split_cols_x6": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_size, c_ptr]),
-    "mgp_expert_x6_workspace_bytes": (c_size, [c_i64, c_i64, c_i32]),
-    "mgp_expert_conditional_x6": (ctypes.c_int, [c_ptr, c_size, c_ptr, c_size, c_ptr, c_i64, c_ptr, c_i64,
-                                                 c_i64, c_i32, c_ptr, c_ptr, c_i64, c_ptr, c_size, c_ptr]),
-    "mgp_expert_conditional_planes": (ctypes.c_int, [c_ptr, c_size, c_ptr, c_size, c_ptr, c_i64, c_ptr, c_i64,
-                                                     c_i64, c_i32, c_i32, c_ptr, c_ptr, c_i64, c_ptr, c_size,
-                                                     c_ptr]),
-    "mgp_split_lower_f16": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i64, c_i32, c_ptr, c_size, c_ptr]),
-    "mgp_split_cols_f16": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_size, c_ptr]),
-    "mgp_trsm_stats_x6_f16": (ctypes.c_int, [c_ptr, c_size, c_ptr, c_size, c_i64, c_i64, c_ptr, c_i64, c_i32,
-                                             c_ptr, c_ptr, c_size, c_ptr, c_i64, c_ptr]),
-    "mgp_rbf_kuf_f16": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_i32,
-                                       c_ptr, c_size, c_ptr]),
-    "mgp_split_upper_f16": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_ptr, c_size, c_ptr]),
-    "mgp_split_upper_f16_bounded": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_ptr, c_size, c_ptr]),
-    "mgp_split_upper_f16_bounded_batch": (ctypes.c_int, [c_i32, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_size, c_ptr]),
-    "mgp_x6_bound_ptr": (ctypes.c_void_p, [c_ptr, c_i64, c_i64, c_i32]),
-    "mgp_trsm_stats_f16": (ctypes.c_int, [c_ptr, c_size, c_ptr, c_size, c_i64, c_i64, c_ptr, c_i64, c_i32,
-                                          c_ptr, c_ptr, c_size, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
-    "mgp_trsm_stats_f16_batch": (ctypes.c_int, [c_i32, c_ptr, c_size, c_ptr, c_size, c_i64, c_i64, c_ptr, c_i64,
-                                                c_i32, c_ptr, c_ptr, c_size, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
-    "mgp_expert_conditional_f16_batch": (ctypes.c_int, [c_i32, c_ptr, c_size, c_ptr, c_size, c_ptr, c_i64, c_ptr,
-                                                        c_i64, c_i64, c_i32, c_ptr, c_ptr, c_i64, c_ptr, c_size,
-                                                        c_ptr, c_size, c_ptr, c_ptr]),
-    "mgp_trsm_stats_f16x8": (ctypes.c_int, [c_ptr, c_size, c_ptr, c_size, c_i64, c_i64, c_ptr, c_i64, c_i32,
-                                            c_ptr, c_ptr, c_size, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
-    "mgp_expert_conditional_f16": (ctypes.c_int, [c_ptr, c_size, c_ptr, c_size, c_ptr, c_i64, c_ptr, c_i64,
-                                                  c_i64, c_i32, c_ptr, c_ptr, c_i64, c_ptr, c_size, c_ptr]),
-    "mgp_expert_conditional_f16x8": (ctypes.c_int, [c_ptr, c_size, c_ptr, c_size, c_ptr, c_i64, c_ptr, c_i64,
-                                                    c_i64, c_i32, c_ptr, c_ptr, c_i64, c_ptr, c_size, c_ptr]),
-    "mgp_kl_workspace_bytes": (c_size, [c_i64, c_i32]),
-    "mgp_qsqrt_workspace_bytes": (c_size, [c_i64, c_i32]),
-    "mgp_qsqrt_images_kl_f16_batch": (ctypes.c_int, [c_i32, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i32, c_ptr,
-                                                     c_size, c_ptr, c_ptr, c_size, c_ptr]),
-    "mgp_gauss_kl_white": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i32, c_ptr,
-                                          c_ptr, c_size, c_ptr]),
-    "mgp_elbo_workspace_bytes": (c_size, [c_i64]),
-    "mgp_elbo_terms": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_i32, ctypes.c_float,
-                                 ctypes.c_float, c_ptr, c_ptr, c_u64, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
-    "mgp_elbo_terms_modified": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_i32,
-                                          ctypes.c_float, ctypes.c_float, c_ptr, c_ptr, c_u64, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
-    "mgp_elbo_backward_workspace_bytes": (c_size, [c_i64, c_i32]),
-    "mgp_elbo_terms_backward": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_i32,
-                                          ctypes.c_float, ctypes.c_float, c_ptr, c_ptr, c_u64, c_i64, ctypes.c_float, c_ptr, c_i64,
-                                          c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "mgp_elbo_combine": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, ctypes.c_double, ctypes.c_double, c_ptr,
-                                        c_ptr, c_ptr]),
-    "mgp_predict_epilogue": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_ptr,
-                                            c_ptr, c_ptr, c_ptr]),
-    "mgp_philox_noise": (ctypes.c_int, [c_u64, c_i64, c_i64, c_i32, c_i32, c_ptr, c_ptr, c_ptr]),
-    "mgp_philox_normal2": (ctypes.c_int, [c_u64, c_i64, c_i64, c_i32, c_i32, c_ptr, c_ptr]),
-    "mgp_predict_samples": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i32, c_i32, ctypes.c_float,
-                                      ctypes.c_float, c_ptr, c_ptr, c_ptr, c_u64, c_i64, c_ptr, c_ptr, c_ptr]),
-    "mgp_elbo_terms_multiclass": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, ctypes.c_float, c_ptr, c_i64, c_i32, c_i32,
-                                            ctypes.c_float, ctypes.c_float, c_ptr, c_ptr, c_u64, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
-    "mgp_elbo_terms_multiclass_backward": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, ctypes.c_float, c_ptr, c_i64, c_i32, c_i32,
-                                                     ctypes.c_float, ctypes.c_float, c_ptr, c_ptr, c_u64, c_i64, ctypes.c_float, c_ptr, c_i64,
-                                                     c_ptr, c_ptr, c_size, c_ptr]),
-    "mgp_multiclass_predict": (ctypes.c_int, [c_ptr, c_ptr, c_i64, c_i64, c_i32, ctypes.c_float, c_ptr, c_ptr,
-                                              c_ptr]),
-    "mgp_predict_samples_multiclass": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, ctypes.c_float, c_i64, c_i32, c_i32, ctypes.c_float,
-                                                 ctypes.c_float, c_ptr, c_ptr, c_ptr, c_u64, c_i64, c_ptr, c_ptr, c_ptr]),
-    "mgp_assign_logits": (ctypes.c_int, [c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i32, c_i32, ctypes.c_float, c_ptr,
-                                         c_u64, c_i64, c_ptr, c_ptr]),
-    "mgp_relaxed_onehot_sample": (ctypes.c_int, [c_ptr, c_i64, c_i32, c_i32, ctypes.c_float, c_ptr, c_u64, c_i64,
-                                                 c_ptr, c_ptr]),
-    "mgp_e_log_p_y": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, ctypes.c_float,
-                                     c_ptr, c_i64, c_i32, c_i32, c_ptr, c_ptr]),
-    # the mixture predictive (csrc/mixture.hip)
-    "mgp_mixture_predict_workspace_bytes": (c_size, [c_i64, c_i32]),
-    "mgp_mixture_predict": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_i32,
-                                           ctypes.c_float, c_ptr, c_u64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
-                                           c_ptr, c_size, c_ptr]),
-    "mgp_mixture_density_grid": (ctypes.c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_i32,
-                                                c_ptr, c_i64, c_ptr]),
-    # CDF, CRPS and quantiles of the mixture predictive (csrc/mixture_score.hip)
-    "mgp_mixture_score_workspace_bytes": (c_size, [c_i64, c_i32]),
-    "mgp_mixture_score": (ctypes.c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr,
-                                         c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "mgp_mixture_quantiles": (ctypes.c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_i32, c_ptr,
-                                             c_i64, c_ptr]),
-    # natural-gradient step on (q_mu, q_sqrt) (csrc/natgrad.hip)
-    "mgp_natgrad_workspace_bytes": (c_size, [c_i64, c_i32]),
-    "mgp_natgrad_step": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64,
-                                        c_i32, c_i64, c_i32, ctypes.c_float, ctypes.c_float, c_ptr, c_ptr, c_size,
-                                        c_ptr]),
-    # pathwise posterior samples (csrc/paths.hip)
-    "mgp_path_eval": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64,
-                                     c_ptr, c_i64, c_i32, c_ptr, c_i64, c_ptr]),
-    # scipy.cluster.vq on the device (csrc/kmeans.hip)
-    "mgp_vq": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_ptr]),
-    "mgp_kmeans_workspace_bytes": (c_size, [c_i64, c_i64, c_i32, c_i32]),
-    "mgp_kmeans_init": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_i64, c_i64, c_i32, c_ptr, c_size,
-                                       c_ptr]),
-    "mgp_kmeans_iterate": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_i64, c_i32, c_i32, ctypes.c_double, c_ptr,
-                                          c_size, c_ptr, c_ptr]),
-    "mgp_kmeans_select": (ctypes.c_int, [c_i64, c_i64, c_i32, c_i32, c_ptr, c_size, c_ptr, c_i64, c_ptr, c_ptr,
-                                         c_ptr]),
-    "mgp_kmeans_update": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr,
-                                         c_size, c_ptr]),
-    # greedy conditional-variance selection of inducing points (csrc/greedy.hip)
-    "mgp_greedy_workspace_bytes": (c_size, [c_i64, c_i64, c_i32]),
-    "mgp_greedy_init": (ctypes.c_int, [c_i64, c_i32, c_ptr, ctypes.c_double, c_ptr, c_size, c_ptr]),
-    "mgp_greedy_steps": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_i32, c_i64, c_i32, c_ptr, c_i64,
-                                        c_ptr, c_size, c_ptr, c_ptr]),
-    "mgp_greedy_result": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_i32, c_i64, c_ptr, c_size, c_ptr, c_ptr, c_i64,
-                                         c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-}
 
-_lib = None
+def _ctype(decl, where, is_return=False):
+    """The ctypes type of one C return type or parameter; an unknown type raises (no width is guessed)."""
+    words = decl.replace("*", " * ").split()
+    if is_return and words == ["const", "char", "*"]:
+        return ctypes.c_char_p   # a C string (mgp_version, mgp_status_string)
+    words = [w for w in words if w != "const"]
+    if "*" in words:
+        return ctypes.c_void_p
+    if not is_return and len(words) == 2:
+        words.pop()   # the parameter's name
+    if len(words) != 1 or words[0] not in _SCALARS:
+        raise MGPLibraryError(f"{where}: type {decl.strip()!r} is outside the C-ABI's vocabulary")
+    return _SCALARS[words[0]]
+
+
+def parse_prototypes(text):
+    """name -> (restype, [argtypes]) of every `ret mgp_name(params);` in the header text."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//.*", "", text)
+    text = re.sub(r"^[ \t]*#(?:.*\\\n)*.*$", "", text, flags=re.M)
+    table = {}
+    for stmt in text.split(";"):
+        m = re.fullmatch(r"\s*(.*?)\b(mgp_\w+)\s*\(([^()]*)\)\s*", re.split(r"[{}]", stmt)[-1], re.S)
+        if not m:
+            if re.search(r"\bmgp_\w+\s*\(", stmt):   # no prototype, no call: never a default int conversion
+                raise MGPLibraryError(f"cannot parse the declaration {' '.join(stmt.split())!r}")
+            continue
+        ret, name, params = m.groups()
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        table[name] = (_ctype(ret, f"{name}: return", is_return=True),
+                       [_ctype(p, f"{name}: parameter {i + 1} ({p.strip()})") for i, p in enumerate(params)])
+    return table
+
+
+def header_prototypes(path=HEADER_PATH):
+    try:
+        with open(path) as f:
+            return parse_prototypes(f.read())
+    except OSError as e:
+        raise MGPLibraryError(f"cannot read the C-ABI header {path}: {e}") from e
 
 
 def header_symbols(path=HEADER_PATH):
     """Every function name declared in include/mgp_hip.h."""
-    text = open(path).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(mgp_[a-z0-9_]+)\s*\(", text)))
+    return sorted(header_prototypes(path))
+
+
+# name -> (restype, argtypes), as include/mgp_hip.h declares them
+SIGNATURES = header_prototypes()
+
+_lib = None
 
 
 def load():
@@ -302,7 +115,27 @@ def check(name, status):
         raise MGPError(name, status, msg)
 
 
+def marshal(arg):
+    """One argument as ctypes takes it: a tensor (anything with data_ptr()) becomes its
+    pointer, a list / tuple of tensors a c_void_p array (None -> NULL); scalars, None
+    and ctypes instances pass through.  Nothing is checked here."""
+    kind = type(arg)
+    if kind is int or kind is float or arg is None:
+        return arg
+    if kind is list or kind is tuple:
+        return (ctypes.c_void_p * len(arg))(*[None if t is None else t.data_ptr() for t in arg])
+    data_ptr = getattr(arg, "data_ptr", None)
+    return arg if data_ptr is None else data_ptr()
+
+
 def call(name, *args):
-    """Call an int-returning entry point and raise MGPError on failure."""
-    fn = getattr(load(), name)
-    check(name, fn(*args))
+    """Call an int-returning entry point on marshalled arguments (the pointer arrays live
+    until it returns) and raise MGPError on failure."""
+    check(name, getattr(load(), name)(*[marshal(a) for a in args]))
+
+
+def call_raw(name, *args):
+    """call without the marshalling pass, for arguments that are ints, floats, None and
+    ctypes instances already: the wrappers of the ELBO step, whose host time is the step
+    time at small sizes, convert their own pointers."""
+    check(name, getattr(load(), name)(*args))

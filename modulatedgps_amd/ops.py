@@ -74,6 +74,32 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
+def _workspace(entry, dims, workspace, device, count=1):
+    """`workspace` if it holds count * entry(*dims) bytes (entry: a *_bytes function of the
+    library), else a new buffer that does."""
+    nbytes = getattr(_lib.load(), entry)(*dims) * count
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = _ws(nbytes, device)
+    return workspace
+
+
+def _ptrs(ts):
+    """The c_void_p array of the tensors' pointers (None -> NULL) for _lib.call_raw: the
+    wrappers of the ELBO step (kuu_potrf_trtri, split_upper_f16_bounded_batch,
+    qsqrt_images_kl_f16_batch, trsm_stats_f16_batch, expert_conditional_f16_batch,
+    elbo_terms, elbo_combine) convert their own pointers, because at small sizes the
+    step's time is the host's and a generic pass over every argument shows in it."""
+    return (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+def _new_workspace(entry, dims, device):
+    """A new workspace of entry(*dims) bytes; 0 bytes is the library refusing the sizes."""
+    nbytes = getattr(_lib.load(), entry)(*dims)
+    if nbytes == 0:
+        _lib.check(entry, 3)
+    return _ws(nbytes, device)
+
+
 # --------------------------------------------------------------------------- K1 / K2
 def rbf_kuf(X, Z, variance, lengthscales, out=None):
     """Kuf = K(Z, X) [M, N] (models.py:139)."""
@@ -84,8 +110,7 @@ def rbf_kuf(X, Z, variance, lengthscales, out=None):
         raise ValueError("X and Z must have the same number of columns")
     if out is None:
         out = padded(M, N, X.device)
-    _lib.call("mgp_rbf_kuf", X.data_ptr(), _ld(X), Z.data_ptr(), _ld(Z), N, M, D,
-              variance.data_ptr(), lengthscales.data_ptr(), lengthscales.numel(), out.data_ptr(),
+    _lib.call("mgp_rbf_kuf", X, _ld(X), Z, _ld(Z), N, M, D, variance, lengthscales, lengthscales.numel(), out,
               _ld(out), _stream())
     return out
 
@@ -96,8 +121,8 @@ def rbf_kuu(Z, variance, lengthscales, jitter, out=None):
     M, D = Z.shape
     if out is None:
         out = padded(M, M, Z.device)
-    _lib.call("mgp_rbf_kuu", Z.data_ptr(), _ld(Z), M, D, variance.data_ptr(), lengthscales.data_ptr(),
-              lengthscales.numel(), float(jitter), out.data_ptr(), _ld(out), _stream())
+    _lib.call("mgp_rbf_kuu", Z, _ld(Z), M, D, variance, lengthscales, lengthscales.numel(), float(jitter), out,
+              _ld(out), _stream())
     return out
 
 
@@ -114,13 +139,10 @@ def potrf_trtri(A, L=None, LinvT=None, info=None, workspace=None):
         LinvT = padded(M, M, dev, batch=Bt)
     if info is None:
         info = torch.empty(Bt, dtype=torch.int32, device=dev)
-    nbytes = _lib.load().mgp_chol_workspace_bytes(M, Bt)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = _ws(nbytes, dev)
+    workspace = _workspace("mgp_chol_workspace_bytes", (M, Bt), workspace, dev)
     if L.stride(0) != LinvT.stride(0) or _ld(L) != _ld(LinvT):
         raise ValueError("L and LinvT must share a layout")
-    _lib.call("mgp_potrf_trtri", A.data_ptr(), _ld(A), A.stride(0), M, Bt, L.data_ptr(),
-              LinvT.data_ptr(), _ld(L), L.stride(0), info.data_ptr(), workspace.data_ptr(),
+    _lib.call("mgp_potrf_trtri", A, _ld(A), A.stride(0), M, Bt, L, LinvT, _ld(L), L.stride(0), info, workspace,
               workspace.numel(), _stream())
     return L, LinvT, info
 
@@ -137,7 +159,6 @@ def kuu_potrf_trtri(Zs, variances, lengthscales, jitter, LinvT=None, L=None, inf
     kuf: (X [N, D], [image per layer], fmt "f16" | "x6"): the factorisation's step
     launches also write each layer's Kuf image K(Z_b, X), bit-identical to
     rbf_kuf_x6(X, Z_b, ..., fmt=fmt) (mgp_kuu_potrf_trtri_kuf)."""
-    import ctypes
     Bt = len(Zs)
     M, D = Zs[0].shape
     ldz = _ld(Zs[0])
@@ -152,48 +173,32 @@ def kuu_potrf_trtri(Zs, variances, lengthscales, jitter, LinvT=None, L=None, inf
         L = padded(M, M, dev, batch=Bt)
     if info is None:
         info = torch.empty(Bt, dtype=torch.int32, device=dev)
-    nbytes = _lib.load().mgp_chol_workspace_bytes(M, Bt)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = _ws(nbytes, dev)
-    P = ctypes.c_void_p * Bt
-    zp = P(*[z.data_ptr() for z in Zs])
-    vp = P(*[v.data_ptr() for v in variances])
-    lp = P(*[l.data_ptr() for l in lengthscales])
+    workspace = _workspace("mgp_chol_workspace_bytes", (M, Bt), workspace, dev)
     nl = (ctypes.c_int32 * Bt)(*[l.numel() for l in lengthscales])
-    if kuf is not None:
-        lib = _lib.load()
+    args = [_ptrs(Zs), ldz, M, D, _ptrs(variances), _ptrs(lengthscales), nl, float(jitter), Bt,
+            L.data_ptr() if L is not None else None, LinvT.data_ptr(), _ld(LinvT), LinvT.stride(0), info.data_ptr(),
+            workspace.data_ptr(), workspace.numel()]
+    # each variant's tail extends the one before it: _ev the event, _ex the bound pointers, _kuf the Kuf images
+    variant = ("_kuf" if kuf is not None else "_ex" if tfr_bound_images is not None
+               else "_ev" if prep_event is not None else "")
+    if variant:
+        args.append(prep_event.cuda_event if prep_event is not None else None)
+    if variant in ("_ex", "_kuf"):
+        bp = None
+        if tfr_bound_images is not None:
+            bound_ptr = _lib.load().mgp_x6_bound_ptr
+            bp = (ctypes.c_void_p * Bt)(*[bound_ptr(t.data_ptr(), M, 0, 1) for t in tfr_bound_images])
+        args.append(bp)
+    if variant == "_kuf":
         X, imgs, fmt = kuf
         _check(X, "X", 2)
         if X.shape[1] != D or len(imgs) != Bt:
             raise ValueError("kuf: X must have Z's D columns and one image per layer")
-        kb = lib.mgp_x6_cols_bytes(M, X.shape[0])
-        if min(t.numel() for t in imgs) < kb:
+        if min(t.numel() for t in imgs) < _lib.load().mgp_x6_cols_bytes(M, X.shape[0]):
             raise ValueError("kuf: an image buffer is smaller than mgp_x6_cols_bytes(M, N)")
-        bp = None
-        if tfr_bound_images is not None:
-            bp = P(*[lib.mgp_x6_bound_ptr(t.data_ptr(), M, 0, 1) for t in tfr_bound_images])
-        _lib.call("mgp_kuu_potrf_trtri_kuf", zp, ldz, M, D, vp, lp, nl, float(jitter), Bt,
-                  L.data_ptr() if L is not None else None, LinvT.data_ptr(), _ld(LinvT),
-                  LinvT.stride(0), info.data_ptr(), workspace.data_ptr(), workspace.numel(),
-                  prep_event.cuda_event if prep_event is not None else None, bp,
-                  X.data_ptr(), _ld(X), X.shape[0], P(*[t.data_ptr() for t in imgs]),
-                  min(t.numel() for t in imgs), {"x6": 0, "f16": 1}[fmt], _stream())
-    elif tfr_bound_images is not None:
-        lib = _lib.load()
-        bp = P(*[lib.mgp_x6_bound_ptr(t.data_ptr(), M, 0, 1) for t in tfr_bound_images])
-        _lib.call("mgp_kuu_potrf_trtri_ex", zp, ldz, M, D, vp, lp, nl, float(jitter), Bt,
-                  L.data_ptr() if L is not None else None, LinvT.data_ptr(), _ld(LinvT),
-                  LinvT.stride(0), info.data_ptr(), workspace.data_ptr(), workspace.numel(),
-                  prep_event.cuda_event if prep_event is not None else None, bp, _stream())
-    elif prep_event is not None:
-        _lib.call("mgp_kuu_potrf_trtri_ev", zp, ldz, M, D, vp, lp, nl, float(jitter), Bt,
-                  L.data_ptr() if L is not None else None, LinvT.data_ptr(), _ld(LinvT),
-                  LinvT.stride(0), info.data_ptr(), workspace.data_ptr(), workspace.numel(),
-                  prep_event.cuda_event, _stream())
-    else:
-        _lib.call("mgp_kuu_potrf_trtri", zp, ldz, M, D, vp, lp, nl, float(jitter), Bt,
-                  L.data_ptr() if L is not None else None, LinvT.data_ptr(), _ld(LinvT),
-                  LinvT.stride(0), info.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream())
+        args += [X.data_ptr(), _ld(X), X.shape[0], _ptrs(imgs), min(t.numel() for t in imgs),
+                 {"x6": 0, "f16": 1}[fmt]]
+    _lib.call_raw("mgp_kuu_potrf_trtri" + variant, *args, _stream())
     return L, LinvT, info
 
 
@@ -235,9 +240,8 @@ def trsm_stats(LinvT, Kuf, q_mu, A=None, stats=None):
     if stats is None:
         T = stats_tiles(M)
         stats = padded(T * (K + 1), N, dev).unflatten(0, (T, K + 1))
-    _lib.call("mgp_trsm_stats", LinvT.data_ptr(), _ld(LinvT), Kuf.data_ptr(), _ld(Kuf), M, N,
-              q_mu.data_ptr(), _ld(q_mu), K, A.data_ptr(), _ld(A), stats.data_ptr(), _ld(stats),
-              _stream())
+    _lib.call("mgp_trsm_stats", LinvT, _ld(LinvT), Kuf, _ld(Kuf), M, N, q_mu, _ld(q_mu), K, A, _ld(A), stats,
+              _ld(stats), _stream())
     return A, stats
 
 
@@ -247,11 +251,9 @@ def rbf_kuf_x6(X, Z, variance, lengthscales, out=None, fmt="x6"):
     _check(X, "X", 2), _check(Z, "Z", 2)
     N, D = X.shape
     M = Z.shape[0]
-    nbytes = _lib.load().mgp_x6_cols_bytes(M, N)
-    if out is None or out.numel() < nbytes:
-        out = _ws(nbytes, X.device)
-    _lib.call("mgp_rbf_kuf_" + _fmt(fmt), X.data_ptr(), _ld(X), Z.data_ptr(), _ld(Z), N, M, D, variance.data_ptr(),
-              lengthscales.data_ptr(), lengthscales.numel(), out.data_ptr(), out.numel(), _stream())
+    out = _workspace("mgp_x6_cols_bytes", (M, N), out, X.device)
+    _lib.call("mgp_rbf_kuf_" + _fmt(fmt), X, _ld(X), Z, _ld(Z), N, M, D, variance, lengthscales, lengthscales.numel(),
+              out, out.numel(), _stream())
     return out
 
 
@@ -262,13 +264,11 @@ def split_upper_x6(LinvT, out=None, fmt="x6", bounded=False):
     mgp_split_upper_f16_bounded)."""
     _check(LinvT, "LinvT", 2)
     M = LinvT.shape[0]
-    nbytes = _lib.load().mgp_x6_lower_bytes(M, 1)
     if bounded and (fmt != "f16" or out is None):
         raise ValueError("bounded splits are split-f16 into the image that received the bound")
-    if out is None or out.numel() < nbytes:
-        out = _ws(nbytes, LinvT.device)
+    out = _workspace("mgp_x6_lower_bytes", (M, 1), out, LinvT.device)
     name = "mgp_split_upper_f16_bounded" if bounded else "mgp_split_upper_" + _fmt(fmt)
-    _lib.call(name, LinvT.data_ptr(), _ld(LinvT), M, out.data_ptr(), out.numel(), _stream())
+    _lib.call(name, LinvT, _ld(LinvT), M, out, out.numel(), _stream())
     return out
 
 
@@ -279,9 +279,8 @@ def split_upper_f16_bounded_batch(LinvT, outs):
     n, M = len(outs), LinvT.shape[1]
     if LinvT.shape[0] < n:
         raise ValueError("one LinvT matrix per image")
-    arr = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
-    _lib.call("mgp_split_upper_f16_bounded_batch", n, LinvT.data_ptr(), _ld(LinvT), LinvT.stride(0), M, arr,
-              min(o.numel() for o in outs), _stream())
+    _lib.call_raw("mgp_split_upper_f16_bounded_batch", n, LinvT.data_ptr(), _ld(LinvT), LinvT.stride(0), M,
+                  _ptrs(outs), min(o.numel() for o in outs), _stream())
     return list(outs)
 
 
@@ -298,32 +297,25 @@ def trsm_stats_x6(Tfr, Kfr, q_mu, M, N, Afr=None, stats=None, A=None, f16_varian
     _check(q_mu, "q_mu", 2)
     K = q_mu.shape[1]
     dev = q_mu.device
-    nbytes = _lib.load().mgp_x6_cols_bytes(M, N)
-    if Afr is None or Afr.numel() < nbytes:
-        Afr = _ws(nbytes, dev)
+    Afr = _workspace("mgp_x6_cols_bytes", (M, N), Afr, dev)
     if stats is None:
         T = stats_tiles(M)
         stats = padded(T * (K + 1), N, dev).unflatten(0, (T, K + 1))
-    if f16_variance is not None:
-        if _fmt(in_fmt) == "x6":
-            if A is not None:
-                raise ValueError("the split-bf16 -> split-f16 K4 does not write the f32 A")
-            _lib.call("mgp_trsm_stats_x6_f16", Tfr.data_ptr(), Tfr.numel(), Kfr.data_ptr(), Kfr.numel(), M, N,
-                      q_mu.data_ptr(), _ld(q_mu), K, f16_variance.data_ptr(), Afr.data_ptr(), Afr.numel(),
-                      stats.data_ptr(), _ld(stats), _stream())
-        else:
-            from .config import expert_cross
-            entry = "mgp_trsm_stats_f16x8" if (cross or expert_cross()) == "f8" else "mgp_trsm_stats_f16"
-            _lib.call(entry, Tfr.data_ptr(), Tfr.numel(), Kfr.data_ptr(), Kfr.numel(), M, N,
-                      q_mu.data_ptr(), _ld(q_mu), K, f16_variance.data_ptr(), Afr.data_ptr(), Afr.numel(),
-                      stats.data_ptr(), _ld(stats), A.data_ptr() if A is not None else None,
-                      _ld(A) if A is not None else N, _stream())
-        return Afr, stats
-    if _fmt(in_fmt) != "x6":
-        raise ValueError("split-f16 K4 inputs need the split-f16 output (f16_variance)")
-    _lib.call("mgp_trsm_stats_x6", Tfr.data_ptr(), Tfr.numel(), Kfr.data_ptr(), Kfr.numel(), M, N,
-              q_mu.data_ptr(), _ld(q_mu), K, Afr.data_ptr(), Afr.numel(), stats.data_ptr(), _ld(stats),
-              A.data_ptr() if A is not None else None, _ld(A) if A is not None else N, _stream())
+    args = [Tfr, Tfr.numel(), Kfr, Kfr.numel(), M, N, q_mu, _ld(q_mu), K]
+    out_args = [Afr, Afr.numel(), stats, _ld(stats)]
+    a_args = [A, _ld(A) if A is not None else N]
+    if f16_variance is None:
+        if _fmt(in_fmt) != "x6":
+            raise ValueError("split-f16 K4 inputs need the split-f16 output (f16_variance)")
+        _lib.call("mgp_trsm_stats_x6", *args, *out_args, *a_args, _stream())
+    elif _fmt(in_fmt) == "x6":
+        if A is not None:
+            raise ValueError("the split-bf16 -> split-f16 K4 does not write the f32 A")
+        _lib.call("mgp_trsm_stats_x6_f16", *args, f16_variance, *out_args, _stream())
+    else:
+        from .config import expert_cross
+        entry = "mgp_trsm_stats_f16x8" if (cross or expert_cross()) == "f8" else "mgp_trsm_stats_f16"
+        _lib.call(entry, *args, f16_variance, *out_args, *a_args, _stream())
     return Afr, stats
 
 
@@ -347,12 +339,10 @@ def trsm_stats_f16_batch(Tfrs, Kfrs, q_mus, M, N, Afrs, statss, variances, As=No
         lda = _ld(As[0])
         if any(_ld(a) != lda for a in As):
             raise ValueError("the f32 A buffers must share a leading dimension")
-
-    def arr(ts):
-        return (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
-    _lib.call("mgp_trsm_stats_f16_batch", n, arr(Tfrs), min(t.numel() for t in Tfrs), arr(Kfrs),
-              min(t.numel() for t in Kfrs), M, N, arr(q_mus), ldq, K, arr(variances), arr(Afrs),
-              min(t.numel() for t in Afrs), arr(statss), lds, arr(As) if As is not None else None, lda, _stream())
+    _lib.call_raw("mgp_trsm_stats_f16_batch", n, _ptrs(Tfrs), min(t.numel() for t in Tfrs), _ptrs(Kfrs),
+                  min(t.numel() for t in Kfrs), M, N, _ptrs(q_mus), ldq, K, _ptrs(variances), _ptrs(Afrs),
+                  min(t.numel() for t in Afrs), _ptrs(statss), lds, _ptrs(As) if As is not None else None, lda,
+                  _stream())
     return list(zip(Afrs, statss))
 
 
@@ -384,13 +374,9 @@ def expert_conditional(A, q_sqrt, stats, variance, fmean=None, fvar=None, worksp
         fvar = padded(K, N, dev)
     if _ld(fmean) != _ld(fvar):
         raise ValueError("fmean and fvar must share a leading dimension")
-    nbytes = _lib.load().mgp_expert_workspace_bytes(M, N, K)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = _ws(nbytes, dev)
-    _lib.call("mgp_expert_conditional_f32", A.data_ptr(), _ld(A), q_sqrt.data_ptr(), _ld(q_sqrt),
-              q_sqrt.stride(0), stats.data_ptr(), _ld(stats), variance.data_ptr(), M, N, K,
-              fmean.data_ptr(), fvar.data_ptr(), _ld(fmean), workspace.data_ptr(),
-              workspace.numel(), _stream())
+    workspace = _workspace("mgp_expert_workspace_bytes", (M, N, K), workspace, dev)
+    _lib.call("mgp_expert_conditional_f32", A, _ld(A), q_sqrt, _ld(q_sqrt), q_sqrt.stride(0), stats, _ld(stats),
+              variance, M, N, K, fmean, fvar, _ld(fmean), workspace, workspace.numel(), _stream())
     return fmean, fvar
 
 
@@ -416,12 +402,10 @@ def full_cov_conditional(X, A, q_sqrt, variance, lengthscales, out=None, workspa
         out = padded(N, N, dev, batch=K)
     elif tuple(out.shape) != (K, N, N):
         raise ValueError(f"out must be [{K}, {N}, {N}]")
-    nbytes = _lib.load().mgp_full_cov_workspace_bytes(M, N, K)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = _ws(nbytes, dev)
-    _lib.call("mgp_full_cov_conditional", X.data_ptr(), _ld(X), N, D, variance.data_ptr(), lengthscales.data_ptr(),
-              lengthscales.numel(), A.data_ptr(), _ld(A), q_sqrt.data_ptr(), _ld(q_sqrt), q_sqrt.stride(0), M, K,
-              out.data_ptr(), _ld(out), out.stride(0), workspace.data_ptr(), workspace.numel(), _stream())
+    workspace = _workspace("mgp_full_cov_workspace_bytes", (M, N, K), workspace, dev)
+    _lib.call("mgp_full_cov_conditional", X, _ld(X), N, D, variance, lengthscales, lengthscales.numel(), A, _ld(A),
+              q_sqrt, _ld(q_sqrt), q_sqrt.stride(0), M, K, out, _ld(out), out.stride(0), workspace, workspace.numel(),
+              _stream())
     return out
 
 
@@ -437,11 +421,8 @@ def split_lower_x6(q_sqrt, out=None, fmt="x6"):
     K5 (fmt "f16": the split-f16 image, mgp_split_lower_f16)."""
     _check(q_sqrt, "q_sqrt", 3)
     K, M = q_sqrt.shape[0], q_sqrt.shape[1]
-    nbytes = _lib.load().mgp_x6_lower_bytes(M, K)
-    if out is None or out.numel() < nbytes:
-        out = _ws(nbytes, q_sqrt.device)
-    _lib.call("mgp_split_lower_" + _fmt(fmt), q_sqrt.data_ptr(), _ld(q_sqrt), q_sqrt.stride(0), M, K,
-              out.data_ptr(), out.numel(), _stream())
+    out = _workspace("mgp_x6_lower_bytes", (M, K), out, q_sqrt.device)
+    _lib.call("mgp_split_lower_" + _fmt(fmt), q_sqrt, _ld(q_sqrt), q_sqrt.stride(0), M, K, out, out.numel(), _stream())
     return out
 
 
@@ -449,7 +430,6 @@ def qsqrt_images_kl_f16_batch(q_mus, q_sqrts, Lfrs, kl_outs, workspace=None):
     """Both layers' split-f16 tril(q_sqrt) images (split_lower_x6(q_sqrt, fmt="f16")) and
     whitened KL terms (gauss_kl_white(q_mu, q_sqrt), float64 [1] each) in three launches
     (mgp_qsqrt_images_kl_f16_batch; bit-identical).  Layers share q_mu / q_sqrt shapes."""
-    import ctypes
     n = len(q_mus)
     q_sqrts = [as_padded(t) for t in q_sqrts]   # float4 rows (no copy for the layers' storage)
     M, K = q_mus[0].shape
@@ -460,15 +440,10 @@ def qsqrt_images_kl_f16_batch(q_mus, q_sqrts, Lfrs, kl_outs, workspace=None):
             raise ValueError("every layer's q_mu [M, K] / q_sqrt [K, M, M] must share shape and strides")
         if kl.dtype != torch.float64 or kl.numel() < 1:
             raise ValueError("kl_out: float64 tensors of at least one element")
-    lib = _lib.load()
-    nbytes = lib.mgp_qsqrt_workspace_bytes(M, K) * n
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = _ws(nbytes, q_mus[0].device)
-    P = ctypes.c_void_p * n
-    _lib.call("mgp_qsqrt_images_kl_f16_batch", n, P(*[t.data_ptr() for t in q_mus]), _ld(q_mus[0]),
-              P(*[t.data_ptr() for t in q_sqrts]), _ld(q_sqrts[0]), q_sqrts[0].stride(0), M, K,
-              P(*[t.data_ptr() for t in Lfrs]), min(t.numel() for t in Lfrs), P(*[t.data_ptr() for t in kl_outs]),
-              workspace.data_ptr(), workspace.numel(), _stream())
+    workspace = _workspace("mgp_qsqrt_workspace_bytes", (M, K), workspace, q_mus[0].device, count=n)
+    _lib.call_raw("mgp_qsqrt_images_kl_f16_batch", n, _ptrs(q_mus), _ld(q_mus[0]), _ptrs(q_sqrts), _ld(q_sqrts[0]),
+                  q_sqrts[0].stride(0), M, K, _ptrs(Lfrs), min(t.numel() for t in Lfrs), _ptrs(kl_outs),
+                  workspace.data_ptr(), workspace.numel(), _stream())
     return Lfrs, kl_outs
 
 
@@ -477,11 +452,8 @@ def split_cols_x6(A, out=None, fmt="x6"):
     (fmt "f16": the split-f16 image, mgp_split_cols_f16)."""
     _check(A, "A", 2)
     M, N = A.shape
-    nbytes = _lib.load().mgp_x6_cols_bytes(M, N)
-    if out is None or out.numel() < nbytes:
-        out = _ws(nbytes, A.device)
-    _lib.call("mgp_split_cols_" + _fmt(fmt), A.data_ptr(), _ld(A), M, N, out.data_ptr(), out.numel(),
-              _stream())
+    out = _workspace("mgp_x6_cols_bytes", (M, N), out, A.device)
+    _lib.call("mgp_split_cols_" + _fmt(fmt), A, _ld(A), M, N, out, out.numel(), _stream())
     return out
 
 
@@ -501,30 +473,23 @@ def expert_conditional_x6(Afr, Lfr, stats, variance, M, N, K, fmean=None, fvar=N
         fvar = padded(K, N, dev)
     if _ld(fmean) != _ld(fvar):
         raise ValueError("fmean and fvar must share a leading dimension")
-    nbytes = _lib.load().mgp_expert_x6_workspace_bytes(M, N, K)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = _ws(nbytes, dev)
+    workspace = _workspace("mgp_expert_x6_workspace_bytes", (M, N, K), workspace, dev)
+    args = [Afr, Afr.numel(), Lfr, Lfr.numel(), stats, _ld(stats), variance, M, N, K]
+    out_args = [fmean, fvar, _ld(fmean), workspace, workspace.numel()]
     if _fmt(fmt) == "f16":
         from .config import expert_cross
         entry = "mgp_expert_conditional_f16x8" if (cross or expert_cross()) == "f8" else "mgp_expert_conditional_f16"
-        args = [Afr.data_ptr(), Afr.numel(), Lfr.data_ptr(), Lfr.numel(), stats.data_ptr(), _ld(stats),
-                variance.data_ptr(), M, N, K, fmean.data_ptr(), fvar.data_ptr(), _ld(fmean), workspace.data_ptr(),
-                workspace.numel()]
         if c_out is not None:
             if entry != "mgp_expert_conditional_f16":
                 raise ValueError("c_out needs f16 cross terms")
             Cfr, colmax = c_out
             entry = "mgp_expert_conditional_f16c"
-            args += [Cfr.data_ptr(), Cfr.numel(), colmax.data_ptr()]
-        _lib.call(entry, *args, _stream())
+            out_args += [Cfr, Cfr.numel(), colmax]
+        _lib.call(entry, *args, *out_args, _stream())
     elif planes == 3:
-        _lib.call("mgp_expert_conditional_x6", Afr.data_ptr(), Afr.numel(), Lfr.data_ptr(), Lfr.numel(),
-                  stats.data_ptr(), _ld(stats), variance.data_ptr(), M, N, K, fmean.data_ptr(),
-                  fvar.data_ptr(), _ld(fmean), workspace.data_ptr(), workspace.numel(), _stream())
+        _lib.call("mgp_expert_conditional_x6", *args, *out_args, _stream())
     else:
-        _lib.call("mgp_expert_conditional_planes", Afr.data_ptr(), Afr.numel(), Lfr.data_ptr(), Lfr.numel(),
-                  stats.data_ptr(), _ld(stats), variance.data_ptr(), M, N, K, int(planes), fmean.data_ptr(),
-                  fvar.data_ptr(), _ld(fmean), workspace.data_ptr(), workspace.numel(), _stream())
+        _lib.call("mgp_expert_conditional_planes", *args, int(planes), *out_args, _stream())
     return fmean, fvar
 
 
@@ -541,15 +506,14 @@ def expert_conditional_f16_batch(Afrs, Lfrs, statss, variances, M, N, K, fmeans,
     lds, ldf = _ld(statss[0]), _ld(fmeans[0])
     if any(_ld(t) != lds for t in statss) or any(_ld(t) != ldf for t in list(fmeans) + list(fvars)):
         raise ValueError("the layers' stats / fmean / fvar must share leading dimensions")
-
-    def arr(ts):
-        return (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
-    cf = arr([c[0] for c in c_outs]) if c_outs is not None else None
-    cm = arr([c[1] for c in c_outs]) if c_outs is not None else None
-    cb = min(c[0].numel() for c in c_outs) if c_outs is not None else 0
-    _lib.call("mgp_expert_conditional_f16_batch", n, arr(Afrs), min(t.numel() for t in Afrs), arr(Lfrs),
-              min(t.numel() for t in Lfrs), arr(statss), lds, arr(variances), M, N, K, arr(fmeans), arr(fvars), ldf,
-              arr(workspaces), min(t.numel() for t in workspaces), cf, cb, cm, _stream())
+    cf = cm = None
+    cb = 0
+    if c_outs is not None:
+        cf, cm = _ptrs([c[0] for c in c_outs]), _ptrs([c[1] for c in c_outs])
+        cb = min(c[0].numel() for c in c_outs)
+    _lib.call_raw("mgp_expert_conditional_f16_batch", n, _ptrs(Afrs), min(t.numel() for t in Afrs), _ptrs(Lfrs),
+                  min(t.numel() for t in Lfrs), _ptrs(statss), lds, _ptrs(variances), M, N, K, _ptrs(fmeans),
+                  _ptrs(fvars), ldf, _ptrs(workspaces), min(t.numel() for t in workspaces), cf, cb, cm, _stream())
     return list(zip(fmeans, fvars))
 
 
@@ -583,30 +547,18 @@ def elbo_terms_backward(mu_f, var_f, mu_a, var_a, Y, lik_var, S, tau=1e-2, noise
         raise ValueError("G must be a [4, K, N] view of [4K][ldg] rows")
     glv = torch.empty(K, dtype=torch.float64, device=dev) if multiclass_eps is None else None
     glva = torch.empty(K, dtype=torch.float64, device=dev) if assign_lik_var is not None else None
-    nbytes = _lib.load().mgp_elbo_backward_workspace_bytes(N, K)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = _ws(nbytes, dev)
-    zp = up = None
+    workspace = _workspace("mgp_elbo_backward_workspace_bytes", (N, K), workspace, dev)
+    z = u = None
     if noise is not None:
         z, u = noise
         z, u = z.contiguous(), u.contiguous()
-        zp, up = z.data_ptr(), u.data_ptr()
+    # the multiclass entry takes epsilon in lik_var's place and has no lik_var gradient
+    entry, lik, g_lik = "mgp_elbo_terms_backward", lik_var, [glv, glva]
     if multiclass_eps is not None:
-        _lib.call("mgp_elbo_terms_multiclass_backward", mu_f.data_ptr(), var_f.data_ptr(), mu_a.data_ptr(),
-                  var_a.data_ptr(), ldf, Y.data_ptr(), float(multiclass_eps),
-                  assign_lik_var.data_ptr() if assign_lik_var is not None else None, N, K, S, float(tau),
-                  float(jitter), zp, up,
-                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset), float(scale), G.data_ptr(), ldg,
-                  glva.data_ptr() if glva is not None else None, workspace.data_ptr(), workspace.numel(),
-                  _stream())
-        return G, glv, glva
-    _lib.call("mgp_elbo_terms_backward", mu_f.data_ptr(), var_f.data_ptr(), mu_a.data_ptr(),
-              var_a.data_ptr(), ldf, Y.data_ptr(), lik_var.data_ptr(),
-              assign_lik_var.data_ptr() if assign_lik_var is not None else None, N, K, S, float(tau),
-              float(jitter), zp, up,
-              int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset), float(scale), G.data_ptr(), ldg,
-              glv.data_ptr(), glva.data_ptr() if glva is not None else None, workspace.data_ptr(),
-              workspace.numel(), _stream())
+        entry, lik, g_lik = "mgp_elbo_terms_multiclass_backward", float(multiclass_eps), [glva]
+    _lib.call(entry, mu_f, var_f, mu_a, var_a, ldf, Y, lik, assign_lik_var, N, K, S, float(tau), float(jitter), z, u,
+              int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset), float(scale), G, ldg, *g_lik, workspace, workspace.numel(),
+              _stream())
     return G, glv, glva
 
 
@@ -624,13 +576,9 @@ def rbf_backward(X, Z, variance, lengthscales, gK, symmetric=False, accumulate=F
         g_var = torch.zeros(1, dtype=torch.float64, device=dev)
     if g_ls is None:
         g_ls = torch.zeros(n_ls, dtype=torch.float64, device=dev)
-    nbytes = _lib.load().mgp_rbf_backward_workspace_bytes(N, M, D)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = _ws(nbytes, dev)
-    _lib.call("mgp_rbf_backward", X.data_ptr(), _ld(X), Z.data_ptr(), _ld(Z), N, M, D, variance.data_ptr(),
-              lengthscales.data_ptr(), n_ls, gK.data_ptr(), _ld(gK), int(symmetric), int(accumulate),
-              gZ.data_ptr(), _ld(gZ), g_var.data_ptr(), g_ls.data_ptr(), workspace.data_ptr(), workspace.numel(),
-              _stream())
+    workspace = _workspace("mgp_rbf_backward_workspace_bytes", (N, M, D), workspace, dev)
+    _lib.call("mgp_rbf_backward", X, _ld(X), Z, _ld(Z), N, M, D, variance, lengthscales, n_ls, gK, _ld(gK),
+              int(symmetric), int(accumulate), gZ, _ld(gZ), g_var, g_ls, workspace, workspace.numel(), _stream())
     return gZ, g_var, g_ls
 
 
@@ -646,9 +594,10 @@ def rbf_backward_batch(X, Zs, variances, lengthscales, gKufs, gKuus, gZs, g_vars
     rbf_backward(Z[b], Z[b], .., gKuu[b], symmetric=True, accumulate=True) into
     gZ[b], g_var[b], g_ls[b], for all layers in three launches (mgp_rbf_backward_batch;
     bit-identical).  accumulate 2: gZ / g_ls overwritten, g_var added to."""
-    import ctypes
     _check(X, "X", 2)
     N, D = X.shape
+    Zs, variances, lengthscales, gKufs, gKuus, gZs, g_vars, g_lss = map(
+        list, (Zs, variances, lengthscales, gKufs, gKuus, gZs, g_vars, g_lss))   # any sequence of tensors
     n = len(Zs)
     M = Zs[0].shape[0]
     n_ls = lengthscales[0].numel()
@@ -658,39 +607,28 @@ def rbf_backward_batch(X, Zs, variances, lengthscales, gKufs, gKuus, gZs, g_vars
             raise ValueError("every layer's Z must be [M, D]")
     if any(t.numel() != n_ls for t in lengthscales):
         raise ValueError("every layer's lengthscales must have the same size")
-    lib = _lib.load()
-    nbytes = lib.mgp_rbf_backward_batch_workspace_bytes(N, M, D) * n
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = _ws(nbytes, X.device)
-    P = ctypes.c_void_p * n
-    ptrs = lambda ts: P(*[t.data_ptr() for t in ts])
-    _lib.call("mgp_rbf_backward_batch", n, X.data_ptr(), _ld(X), N, ptrs(Zs), _same_ld(Zs, "Z"), M, D,
-              ptrs(variances), ptrs(lengthscales), n_ls, ptrs(gKufs), _same_ld(gKufs, "gKuf"), ptrs(gKuus),
-              _same_ld(gKuus, "gKuu"), int(accumulate), ptrs(gZs), _same_ld(gZs, "gZ"), ptrs(g_vars), ptrs(g_lss),
-              workspace.data_ptr(), workspace.numel(), _stream())
+    workspace = _workspace("mgp_rbf_backward_batch_workspace_bytes", (N, M, D), workspace, X.device, count=n)
+    _lib.call("mgp_rbf_backward_batch", n, X, _ld(X), N, Zs, _same_ld(Zs, "Z"), M, D, variances, lengthscales, n_ls,
+              gKufs, _same_ld(gKufs, "gKuf"), gKuus, _same_ld(gKuus, "gKuu"), int(accumulate), gZs,
+              _same_ld(gZs, "gZ"), g_vars, g_lss, workspace, workspace.numel(), _stream())
     return gZs, g_vars, g_lss
 
 
 def chol_backward_batch(Ls, LinvTs, gLs, outs=None, workspace=None):
     """chol_backward for every layer (same M) in five launches (mgp_chol_backward_batch;
     bit-identical): list of gKuu [M, M]."""
-    import ctypes
+    Ls, LinvTs, gLs = list(Ls), list(LinvTs), list(gLs)   # any sequence of tensors
     n = len(Ls)
     M = Ls[0].shape[0]
-    for t in list(Ls) + list(LinvTs) + list(gLs):
+    for t in Ls + LinvTs + gLs:
         _check(t, "L / LinvT / gL", 2)
         if tuple(t.shape) != (M, M):
             raise ValueError("every layer's L, LinvT and gL must be [M, M]")
     if outs is None:
         outs = [padded(M, M, Ls[0].device) for _ in range(n)]
-    nbytes = _lib.load().mgp_chol_backward_workspace_bytes(M) * n
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = _ws(nbytes, Ls[0].device)
-    P = ctypes.c_void_p * n
-    ptrs = lambda ts: P(*[t.data_ptr() for t in ts])
-    _lib.call("mgp_chol_backward_batch", n, ptrs(Ls), _same_ld(Ls, "L"), ptrs(LinvTs), _same_ld(LinvTs, "LinvT"),
-              ptrs(gLs), _same_ld(gLs, "gL"), M, ptrs(outs), _same_ld(outs, "gKuu"), workspace.data_ptr(),
-              workspace.numel(), _stream())
+    workspace = _workspace("mgp_chol_backward_workspace_bytes", (M,), workspace, Ls[0].device, count=n)
+    _lib.call("mgp_chol_backward_batch", n, Ls, _same_ld(Ls, "L"), LinvTs, _same_ld(LinvTs, "LinvT"), gLs,
+              _same_ld(gLs, "gL"), M, list(outs), _same_ld(outs, "gKuu"), workspace, workspace.numel(), _stream())
     return outs
 
 
@@ -700,20 +638,17 @@ def chol_backward(L, LinvT, gL, out=None, workspace=None):
     M = L.shape[0]
     if out is None:
         out = padded(M, M, L.device)
-    nbytes = _lib.load().mgp_chol_backward_workspace_bytes(M)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = _ws(nbytes, L.device)
-    _lib.call("mgp_chol_backward", L.data_ptr(), _ld(L), LinvT.data_ptr(), _ld(LinvT), gL.data_ptr(), _ld(gL), M,
-              out.data_ptr(), _ld(out), workspace.data_ptr(), workspace.numel(), _stream())
+    workspace = _workspace("mgp_chol_backward_workspace_bytes", (M,), workspace, L.device)
+    _lib.call("mgp_chol_backward", L, _ld(L), LinvT, _ld(LinvT), gL, _ld(gL), M, out, _ld(out), workspace,
+              workspace.numel(), _stream())
     return out
 
 
 def kl_grad(q_mu, q_sqrt, num_data, g_q_mu, g_q_sqrt):
     """Fold -KL / num_data into the ELBO gradients (in place)."""
     M, K = q_mu.shape
-    _lib.call("mgp_kl_grad", q_mu.data_ptr(), _ld(q_mu), q_sqrt.data_ptr(), _ld(q_sqrt), q_sqrt.stride(0), M, K,
-              float(num_data), g_q_mu.data_ptr(), _ld(g_q_mu), g_q_sqrt.data_ptr(), _ld(g_q_sqrt),
-              g_q_sqrt.stride(0), _stream())
+    _lib.call("mgp_kl_grad", q_mu, _ld(q_mu), q_sqrt, _ld(q_sqrt), q_sqrt.stride(0), M, K, float(num_data), g_q_mu,
+              _ld(g_q_mu), g_q_sqrt, _ld(g_q_sqrt), g_q_sqrt.stride(0), _stream())
 
 
 def adam_step(theta, grad, m1, m2, t, lr, u=None, beta1=0.9, beta2=0.999, eps=1e-7, grad_sign=-1.0):
@@ -722,9 +657,8 @@ def adam_step(theta, grad, m1, m2, t, lr, u=None, beta1=0.9, beta2=0.999, eps=1e
     rows, cols = theta.shape
     if grad.shape[-1] != cols:
         raise ValueError("gradient / parameter shape mismatch")
-    _lib.call("mgp_adam_step", theta.data_ptr(), u.data_ptr() if u is not None else None, grad.data_ptr(),
-              int(grad.dtype == torch.float64), _ld(grad), m1.data_ptr(), m2.data_ptr(), rows, cols, _ld(theta),
-              float(lr), float(beta1), float(beta2), float(eps), int(t), float(grad_sign), _stream())
+    _lib.call("mgp_adam_step", theta, u, grad, int(grad.dtype == torch.float64), _ld(grad), m1, m2, rows, cols,
+              _ld(theta), float(lr), float(beta1), float(beta2), float(eps), int(t), float(grad_sign), _stream())
 
 
 class AdamSet:
@@ -733,22 +667,18 @@ class AdamSet:
     None); the pointer arrays of the fixed state are built once."""
 
     def __init__(self, blocks):
-        import ctypes
         n = len(blocks)
         if not 1 <= n <= 16:
             raise ValueError("AdamSet takes 1 .. 16 parameter blocks")
-        P, I64 = ctypes.c_void_p * n, ctypes.c_int64 * n
+        I64 = ctypes.c_int64 * n
         self.n = n
         self.shapes = [tuple(th.shape) for th, *_ in blocks]
-        self.theta = P(*[th.data_ptr() for th, *_ in blocks])
-        self.u = P(*[(u.data_ptr() if u is not None else None) for *_, u in blocks])
-        self.m1 = P(*[m1.data_ptr() for _, m1, _, _ in blocks])
-        self.m2 = P(*[m2.data_ptr() for _, _, m2, _ in blocks])
+        self.theta, self.m1, self.m2, self.u = (_lib.marshal(list(ts)) for ts in zip(*blocks))
         self.rows = I64(*[s[0] for s in self.shapes])
         self.cols = I64(*[s[1] for s in self.shapes])
         self.ld = I64(*[_ld(th) for th, *_ in blocks])
         self._keep = blocks
-        self._P, self._I64, self._I32 = P, I64, ctypes.c_int32 * n
+        self._I64, self._I32 = I64, ctypes.c_int32 * n
 
     def step(self, grads, t, lr, beta1=0.9, beta2=0.999, eps=1e-7, grad_sign=-1.0):
         """grads: one 2-D gradient per block, in order (float32 or float64)."""
@@ -765,17 +695,14 @@ class AdamSet:
                 raise ValueError(f"gradient {j}: dtype {gr.dtype} (float32 or float64 expected)")
             if gr.numel() and (gr.stride(-1) != 1 or gr.device != dev):
                 raise ValueError(f"gradient {j}: must be row-contiguous on {dev}")
-        _lib.call("mgp_adam_step_set", self.n, self.theta, self.u, self._P(*[gr.data_ptr() for gr in grads]),
+        _lib.call("mgp_adam_step_set", self.n, self.theta, self.u, list(grads),
                   self._I32(*[int(gr.dtype == torch.float64) for gr in grads]), self._I64(*[_ld(gr) for gr in grads]),
                   self.m1, self.m2, self.rows, self.cols, self.ld, float(lr), float(beta1), float(beta2), float(eps),
                   int(t), float(grad_sign), _stream())
 
 
 def natgrad_workspace(M, K, device):
-    nbytes = _lib.load().mgp_natgrad_workspace_bytes(M, K)
-    if nbytes == 0:
-        _lib.check("mgp_natgrad_workspace_bytes", 3)
-    return _ws(nbytes, device)
+    return _new_workspace("mgp_natgrad_workspace_bytes", (M, K), device)
 
 
 def natgrad_step(q_mu, q_sqrt, g_q_mu, g_q_sqrt, step, grad_sign=-1.0, info=None, workspace=None):
@@ -801,10 +728,9 @@ def natgrad_step(q_mu, q_sqrt, g_q_mu, g_q_sqrt, step, grad_sign=-1.0, info=None
     nbytes = _lib.load().mgp_natgrad_workspace_bytes(M, K)
     if workspace is None or workspace.numel() < nbytes:
         workspace = natgrad_workspace(M, K, q_mu.device)
-    _lib.call("mgp_natgrad_step", q_mu.data_ptr(), _ld(q_mu), q_sqrt.data_ptr(), _ld(q_sqrt), q_sqrt.stride(0),
-              g_q_mu.data_ptr(), _ld(g_q_mu), g_q_sqrt.data_ptr(), _ld(g_q_sqrt), g_q_sqrt.stride(0),
-              int(g_q_mu.dtype == torch.float64), M, K, float(step), float(grad_sign), info.data_ptr(),
-              workspace.data_ptr(), workspace.numel(), _stream())
+    _lib.call("mgp_natgrad_step", q_mu, _ld(q_mu), q_sqrt, _ld(q_sqrt), q_sqrt.stride(0), g_q_mu, _ld(g_q_mu),
+              g_q_sqrt, _ld(g_q_sqrt), g_q_sqrt.stride(0), int(g_q_mu.dtype == torch.float64), M, K, float(step),
+              float(grad_sign), info, workspace, workspace.numel(), _stream())
     return info
 
 
@@ -816,11 +742,9 @@ def gram(X, Y, N=None, alpha=1.0, tri=False, out=None, workspace=None):
     dev = X.device
     if out is None:
         out = padded(MI, MJ, dev)
-    nbytes = _lib.load().mgp_gram_workspace_bytes(MI, MJ, N, int(tri))
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = _ws(nbytes, dev)
-    _lib.call("mgp_gram", X.data_ptr(), _ld(X), MI, Y.data_ptr(), _ld(Y), MJ, N, float(alpha), int(tri),
-              out.data_ptr(), _ld(out), workspace.data_ptr(), workspace.numel(), _stream())
+    workspace = _workspace("mgp_gram_workspace_bytes", (MI, MJ, N, int(tri)), workspace, dev)
+    _lib.call("mgp_gram", X, _ld(X), MI, Y, _ld(Y), MJ, N, float(alpha), int(tri), out, _ld(out), workspace,
+              workspace.numel(), _stream())
     return out
 
 
@@ -830,11 +754,8 @@ def split_rows_f16(X, bound, N=None, out=None):
     _check(X, "X", 2)
     M = X.shape[0]
     N = X.shape[1] if N is None else N
-    nbytes = _lib.load().mgp_rows_f16_bytes(M, N)
-    if out is None or out.numel() < nbytes:
-        out = _ws(nbytes, X.device)
-    _lib.call("mgp_split_rows_f16", X.data_ptr(), _ld(X), M, N, bound.data_ptr(), out.data_ptr(), out.numel(),
-              _stream())
+    out = _workspace("mgp_rows_f16_bytes", (M, N), out, X.device)
+    _lib.call("mgp_split_rows_f16", X, _ld(X), M, N, bound, out, out.numel(), _stream())
     return out
 
 
@@ -856,26 +777,17 @@ def gram_x6(X, Y, W=None, alpha=1.0, mode=0, N=None, out=None, workspace=None, b
     sx = X3.stride(0) if X3.shape[0] > 1 else 0
     sy = Y3.stride(0) if Y3.shape[0] > 1 else 0
     sw = (W.stride(0) if W.dim() == 2 and W.shape[0] > 1 else 0) if W is not None else 0
-    nbytes = _lib.load().mgp_gram_x6_workspace_bytes(MI, MJ, N, B, int(mode))
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = _ws(nbytes, dev)
+    workspace = _workspace("mgp_gram_x6_workspace_bytes", (MI, MJ, N, B, int(mode)), workspace, dev)
     so = out.stride(0) if out.dim() == 3 else MI * _ld(out)
+    entry, xy_args, bound_args = "mgp_gram_x6", [X3, X3.stride(1), sx, MI, Y3, Y3.stride(1), sy, MJ], ()
     if x_rows is not None:
-        xb, yb, wb = bounds
-        _lib.call("mgp_gram_f16_rows", x_rows.data_ptr(), x_rows.numel(), MI, Y3.data_ptr(), Y3.stride(1), MJ,
-                  W.data_ptr(), sw, N, B, float(alpha), int(mode), out.data_ptr(), out.stride(-2), so,
-                  xb.data_ptr(), yb.data_ptr(), wb.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream())
-        return out
-    if bounds is not None:
-        xb, yb, wb = bounds
-        _lib.call("mgp_gram_f16", X3.data_ptr(), X3.stride(1), sx, MI, Y3.data_ptr(), Y3.stride(1), sy, MJ,
-                  W.data_ptr() if W is not None else None, sw, N, B, float(alpha), int(mode), out.data_ptr(),
-                  out.stride(-2), so, xb.data_ptr(), yb.data_ptr(), wb.data_ptr() if wb is not None else None,
-                  workspace.data_ptr(), workspace.numel(), _stream())
-        return out
-    _lib.call("mgp_gram_x6", X3.data_ptr(), X3.stride(1), sx, MI, Y3.data_ptr(), Y3.stride(1), sy, MJ,
-              W.data_ptr() if W is not None else None, sw, N, B, float(alpha), int(mode), out.data_ptr(),
-              out.stride(-2), so, workspace.data_ptr(), workspace.numel(), _stream())
+        if W is None or any(b is None for b in bounds):
+            raise ValueError("x_rows needs W and all three bounds")
+        entry, xy_args, bound_args = "mgp_gram_f16_rows", [x_rows, x_rows.numel(), MI, Y3, Y3.stride(1), MJ], bounds
+    elif bounds is not None:
+        entry, bound_args = "mgp_gram_f16", bounds
+    _lib.call(entry, *xy_args, W, sw, N, B, float(alpha), int(mode), out, out.stride(-2), so, *bound_args, workspace,
+              workspace.numel(), _stream())
     return out
 
 
@@ -889,11 +801,9 @@ def conditional_backward_prep(q_sqrt, l_bound, out=None):
     prep=...) (mgp_conditional_backward_prep_f16c)."""
     _check(q_sqrt, "q_sqrt", 3)
     K, M, _ = q_sqrt.shape
-    nbytes = _lib.load().mgp_conditional_backward_prep_bytes(M, K)
-    if out is None or out.numel() < nbytes:
-        out = _ws(nbytes, q_sqrt.device)
-    _lib.call("mgp_conditional_backward_prep_f16c", q_sqrt.data_ptr(), _ld(q_sqrt), q_sqrt.stride(0), M, K,
-              l_bound.data_ptr(), out.data_ptr(), out.numel(), _stream())
+    out = _workspace("mgp_conditional_backward_prep_bytes", (M, K), out, q_sqrt.device)
+    _lib.call("mgp_conditional_backward_prep_f16c", q_sqrt, _ld(q_sqrt), q_sqrt.stride(0), M, K, l_bound, out,
+              out.numel(), _stream())
     return out
 
 
@@ -911,9 +821,7 @@ def conditional_backward_x6(Afr, A, q_sqrt, q_mu, LinvT, Gmu, Gv, M, N, out=None
         out = {"g_q_mu": padded(M, K, dev), "g_q_sqrt": padded(M, M, dev, batch=K),
                "g_Kuf": padded(M, N, dev), "g_Lm": padded(M, M, dev),
                "g_var": torch.empty(1, dtype=torch.float64, device=dev)}
-    nbytes = _lib.load().mgp_conditional_backward_workspace_bytes(M, N, K)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = _ws(nbytes, dev)
+    workspace = _workspace("mgp_conditional_backward_workspace_bytes", (M, N, K), workspace, dev)
     if _ld(Gmu) != _ld(Gv):
         raise ValueError("Gmu and Gv must share a leading dimension")
     o = out
@@ -921,21 +829,19 @@ def conditional_backward_x6(Afr, A, q_sqrt, q_mu, LinvT, Gmu, Gv, M, N, out=None
     entry = "mgp_conditional_backward_" + _fmt(fmt)
     if entry.endswith("f16") and (cross or expert_cross()) == "f8":
         entry += "x8"
-    args = [Afr.data_ptr(), Afr.numel(), A.data_ptr(), _ld(A),
-            q_sqrt.data_ptr(), _ld(q_sqrt), q_sqrt.stride(0), q_mu.data_ptr(), _ld(q_mu),
-            LinvT.data_ptr(), _ld(LinvT), Gmu.data_ptr(), Gv.data_ptr(), _ld(Gmu), M, N, K,
-            o["g_q_mu"].data_ptr(), _ld(o["g_q_mu"]), o["g_q_sqrt"].data_ptr(), _ld(o["g_q_sqrt"]),
-            o["g_q_sqrt"].stride(0), o["g_Kuf"].data_ptr(), _ld(o["g_Kuf"]), o["g_Lm"].data_ptr(),
-            _ld(o["g_Lm"]), o["g_var"].data_ptr(), workspace.data_ptr(), workspace.numel()]
+    args = [Afr, Afr.numel(), A, _ld(A), q_sqrt, _ld(q_sqrt), q_sqrt.stride(0), q_mu, _ld(q_mu), LinvT, _ld(LinvT),
+            Gmu, Gv, _ld(Gmu), M, N, K, o["g_q_mu"], _ld(o["g_q_mu"]), o["g_q_sqrt"], _ld(o["g_q_sqrt"]),
+            o["g_q_sqrt"].stride(0), o["g_Kuf"], _ld(o["g_Kuf"]), o["g_Lm"], _ld(o["g_Lm"]), o["g_var"], workspace,
+            workspace.numel()]
     if c_images is not None:
         if entry != "mgp_conditional_backward_f16":
             raise ValueError("c_images need the split-f16 format with f16 cross terms")
         Cfr, colmax, l_bound = c_images
         entry = "mgp_conditional_backward_f16c"
-        args += [Cfr.data_ptr(), Cfr.numel(), colmax.data_ptr(), l_bound.data_ptr()]
+        args += [Cfr, Cfr.numel(), colmax, l_bound]
         if prep is not None:   # from conditional_backward_prep(q_sqrt, l_bound) of the same q_sqrt
             entry += "_prepped"   # t_bound: max |LinvT| (e.g. image_bound of K3's bounded L^-T image)
-            args += [prep.data_ptr(), prep.numel(), t_bound.data_ptr() if t_bound is not None else None]
+            args += [prep, prep.numel(), t_bound]
     elif prep is not None:
         raise ValueError("prep needs c_images (the C-images backward)")
     _lib.call(entry, *args, _stream())
@@ -953,7 +859,7 @@ def colnorm_max(q_sqrt, out=None):
     if out is None:
         out = torch.empty(1, dtype=torch.float32, device=q_sqrt.device)
     K, M = q_sqrt.shape[0], q_sqrt.shape[1]
-    _lib.call("mgp_colnorm_max", q_sqrt.data_ptr(), _ld(q_sqrt), q_sqrt.stride(0), M, K, out.data_ptr(), _stream())
+    _lib.call("mgp_colnorm_max", q_sqrt, _ld(q_sqrt), q_sqrt.stride(0), M, K, out, _stream())
     return out
 
 
@@ -974,12 +880,9 @@ def gauss_kl_white(q_mu, q_sqrt, out=None, workspace=None):
     dev = q_mu.device
     if out is None:
         out = torch.empty(1, dtype=torch.float64, device=dev)
-    nbytes = _lib.load().mgp_kl_workspace_bytes(M, K)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = _ws(nbytes, dev)
-    _lib.call("mgp_gauss_kl_white", q_mu.data_ptr(), _ld(q_mu), q_sqrt.data_ptr(), _ld(q_sqrt),
-              q_sqrt.stride(0), M, K, out.data_ptr(), workspace.data_ptr(), workspace.numel(),
-              _stream())
+    workspace = _workspace("mgp_kl_workspace_bytes", (M, K), workspace, dev)
+    _lib.call("mgp_gauss_kl_white", q_mu, _ld(q_mu), q_sqrt, _ld(q_sqrt), q_sqrt.stride(0), M, K, out, workspace,
+              workspace.numel(), _stream())
     return out
 
 
@@ -1005,38 +908,28 @@ def elbo_terms(mu_f, var_f, mu_a, var_a, Y, lik_var, S, tau=1e-2, noise=None, se
         raise ValueError("Y must be contiguous with N elements")
     if out is None:
         out = torch.empty(1, dtype=torch.float64, device=dev)
-    nbytes = _lib.load().mgp_elbo_workspace_bytes(N)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = _ws(nbytes, dev)
-    zp = up = None
+    workspace = _workspace("mgp_elbo_workspace_bytes", (N,), workspace, dev)
+    z = u = None
     if noise is not None:
         z, u = noise
         _check(z, "noise_z", 3), _check(u, "noise_u", 3)
         if tuple(z.shape) != (S, N, K) or tuple(u.shape) != (S, N, K):
             raise ValueError("explicit noise must be [S, N, K]")
         z, u = z.contiguous(), u.contiguous()
-        zp, up = z.data_ptr(), u.data_ptr()
-    if multiclass_eps is not None:
-        if assign_lik_var is not None:
-            _check(assign_lik_var, "assign_lik_var")
-        _lib.call("mgp_elbo_terms_multiclass", mu_f.data_ptr(), var_f.data_ptr(), mu_a.data_ptr(),
-                  var_a.data_ptr(), ldf, Y.data_ptr(), float(multiclass_eps),
-                  assign_lik_var.data_ptr() if assign_lik_var is not None else None, N, K, S, float(tau),
-                  float(jitter), zp, up,
-                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset), out.data_ptr(), workspace.data_ptr(),
-                  workspace.numel(), _stream())
-        return out
     if assign_lik_var is not None:
         _check(assign_lik_var, "assign_lik_var")
-        _lib.call("mgp_elbo_terms_modified", mu_f.data_ptr(), var_f.data_ptr(), mu_a.data_ptr(),
-                  var_a.data_ptr(), ldf, Y.data_ptr(), lik_var.data_ptr(), assign_lik_var.data_ptr(), N, K,
-                  S, float(tau), float(jitter), zp, up, int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset), out.data_ptr(),
-                  workspace.data_ptr(), workspace.numel(), _stream())
-        return out
-    _lib.call("mgp_elbo_terms", mu_f.data_ptr(), var_f.data_ptr(), mu_a.data_ptr(), var_a.data_ptr(),
-              ldf, Y.data_ptr(), lik_var.data_ptr(), N, K, S, float(tau), float(jitter), zp, up,
-              int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset), out.data_ptr(), workspace.data_ptr(),
-              workspace.numel(), _stream())
+    # the entries differ in the likelihood arguments after Y only
+    alv = assign_lik_var.data_ptr() if assign_lik_var is not None else None
+    if multiclass_eps is not None:
+        entry, lik_args = "mgp_elbo_terms_multiclass", [float(multiclass_eps), alv]
+    elif assign_lik_var is not None:
+        entry, lik_args = "mgp_elbo_terms_modified", [lik_var.data_ptr(), alv]
+    else:
+        entry, lik_args = "mgp_elbo_terms", [lik_var.data_ptr()]
+    _lib.call_raw(entry, mu_f.data_ptr(), var_f.data_ptr(), mu_a.data_ptr(), var_a.data_ptr(), ldf, Y.data_ptr(),
+                  *lik_args, N, K, S, float(tau), float(jitter), z.data_ptr() if z is not None else None,
+                  u.data_ptr() if u is not None else None, int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset),
+                  out.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream())
     return out
 
 
@@ -1046,8 +939,8 @@ def elbo_combine(data_sum, kl_f, kl_a, n_batch, num_data, out=None, out64=None):
         out = torch.empty((), dtype=F32, device=dev)
     if out64 is None:
         out64 = torch.empty((), dtype=torch.float64, device=dev)
-    _lib.call("mgp_elbo_combine", data_sum.data_ptr(), kl_f.data_ptr(), kl_a.data_ptr(),
-              float(n_batch), float(num_data), out.data_ptr(), out64.data_ptr(), _stream())
+    _lib.call_raw("mgp_elbo_combine", data_sum.data_ptr(), kl_f.data_ptr(), kl_a.data_ptr(), float(n_batch),
+                  float(num_data), out.data_ptr(), out64.data_ptr(), _stream())
     return out, out64
 
 
@@ -1059,28 +952,20 @@ def predict_epilogue(fmean, fvar, amean, lik_var, want_y=True, want_assign=False
     ym = torch.empty(N, K, dtype=F32, device=dev) if want_y else None
     yv = torch.empty(N, K, dtype=F32, device=dev) if want_y else None
     asg = torch.empty(N, K, dtype=F32, device=dev) if want_assign else None
-    _lib.call("mgp_predict_epilogue", fmean.data_ptr() if fmean is not None else None,
-              fvar.data_ptr() if fvar is not None else None,
-              amean.data_ptr() if amean is not None else None, _ld(ref),
-              lik_var.data_ptr() if lik_var is not None else None, N, K,
-              ym.data_ptr() if ym is not None else None, yv.data_ptr() if yv is not None else None,
-              asg.data_ptr() if asg is not None else None, _stream())
+    _lib.call("mgp_predict_epilogue", fmean, fvar, amean, _ld(ref), lik_var, N, K, ym, yv, asg, _stream())
     return ym, yv, asg
 
 
 def philox_noise(seed, n_offset, N, K, S, device, want_z=True, want_u=True):
     z = torch.empty(S, N, K, dtype=F32, device=device) if want_z else None
     u = torch.empty(S, N, K, dtype=F32, device=device) if want_u else None
-    _lib.call("mgp_philox_noise", int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset), N, K, S,
-              z.data_ptr() if z is not None else None, u.data_ptr() if u is not None else None,
-              _stream())
+    _lib.call("mgp_philox_noise", int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset), N, K, S, z, u, _stream())
     return z, u
 
 
 def philox_normal2(seed, n_offset, N, K, S, device):
     z = torch.empty(S, N, K, dtype=F32, device=device)
-    _lib.call("mgp_philox_normal2", int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset), N, K, S,
-              z.data_ptr(), _stream())
+    _lib.call("mgp_philox_normal2", int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset), N, K, S, z, _stream())
     return z
 
 
@@ -1093,22 +978,19 @@ def predict_samples(mu_f, var_f, mu_a, var_a, lik_var, S, tau=1e-2, noise=None, 
     dev = mu_f.device
     sy = torch.empty(S, N, dtype=F32, device=dev)
     sf = torch.empty(S, N, dtype=F32, device=dev)
-    ptrs = [None, None, None]
-    if noise is not None:
+    if noise is None:
+        noise = [None, None, None]
+    else:
         noise = [t.contiguous() for t in noise]
         for t in noise:
             _check(t, "noise", 3)
             if tuple(t.shape) != (S, N, K):
                 raise ValueError("explicit noise must be [S, N, K]")
-        ptrs = [t.data_ptr() for t in noise]
+    entry, lik = "mgp_predict_samples", lik_var
     if multiclass_eps is not None:
-        _lib.call("mgp_predict_samples_multiclass", mu_f.data_ptr(), var_f.data_ptr(), mu_a.data_ptr(),
-                  var_a.data_ptr(), _ld(mu_f), float(multiclass_eps), N, K, S, float(tau), float(jitter), *ptrs,
-                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset), sy.data_ptr(), sf.data_ptr(), _stream())
-        return sy, sf
-    _lib.call("mgp_predict_samples", mu_f.data_ptr(), var_f.data_ptr(), mu_a.data_ptr(),
-              var_a.data_ptr(), _ld(mu_f), lik_var.data_ptr(), N, K, S, float(tau), float(jitter), *ptrs,
-              int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset), sy.data_ptr(), sf.data_ptr(), _stream())
+        entry, lik = "mgp_predict_samples_multiclass", float(multiclass_eps)
+    _lib.call(entry, mu_f, var_f, mu_a, var_a, _ld(mu_f), lik, N, K, S, float(tau), float(jitter), *noise,
+              int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset), sy, sf, _stream())
     return sy, sf
 
 
@@ -1120,8 +1002,7 @@ def multiclass_predict(fmean, fvar, epsilon):
         raise ValueError("fmean and fvar must share a leading dimension")
     ym = torch.empty(N, K, dtype=F32, device=fmean.device)
     yv = torch.empty(N, K, dtype=F32, device=fmean.device)
-    _lib.call("mgp_multiclass_predict", fmean.data_ptr(), fvar.data_ptr(), _ld(fmean), N, K, float(epsilon),
-              ym.data_ptr(), yv.data_ptr(), _stream())
+    _lib.call("mgp_multiclass_predict", fmean, fvar, _ld(fmean), N, K, float(epsilon), ym, yv, _stream())
     return ym, yv
 
 
@@ -1139,15 +1020,13 @@ def assign_logits(mu_a, var_a, S, N, stride_s=0, noise_z=None, seed=0, n_offset=
     _latents_check(mu_a, var_a, "a")
     K = mu_a.shape[0]
     out = torch.empty(S, N, K, dtype=F32, device=mu_a.device)
-    zp = None
     if noise_z is not None:
         _check(noise_z, "noise_z", 3)
         if tuple(noise_z.shape) != (S, N, K):
             raise ValueError("explicit noise must be [S, N, K]")
         noise_z = noise_z.contiguous()
-        zp = noise_z.data_ptr()
-    _lib.call("mgp_assign_logits", mu_a.data_ptr(), var_a.data_ptr(), _ld(mu_a), int(stride_s), N, K, S,
-              float(jitter), zp, int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset), out.data_ptr(), _stream())
+    _lib.call("mgp_assign_logits", mu_a, var_a, _ld(mu_a), int(stride_s), N, K, S, float(jitter), noise_z,
+              int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset), out, _stream())
     return out
 
 
@@ -1159,15 +1038,13 @@ def relaxed_onehot_sample(logits, S, N, tau=1e-2, noise_u=None, seed=0, n_offset
         raise ValueError("logits must hold S * N rows of K")
     logits = logits.contiguous()
     W = torch.empty(S * N, K, dtype=F32, device=logits.device)
-    up = None
     if noise_u is not None:
         _check(noise_u, "noise_u")
         if noise_u.numel() != S * N * K:
             raise ValueError("explicit noise must be [S, N, K]")
         noise_u = noise_u.contiguous()
-        up = noise_u.data_ptr()
-    _lib.call("mgp_relaxed_onehot_sample", logits.data_ptr(), N, K, S, float(tau), up,
-              int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset), W.data_ptr(), _stream())
+    _lib.call("mgp_relaxed_onehot_sample", logits, N, K, S, float(tau), noise_u, int(seed) & 0xFFFFFFFFFFFFFFFF,
+              int(n_offset), W, _stream())
     return W
 
 
@@ -1191,10 +1068,9 @@ def e_log_p_y(mu_f, var_f, Y, lik_var, W, S, N, stride_s=0, mu_a=None, var_a=Non
         if _ld(mu_a) != _ld(mu_f):
             raise ValueError("the two layers' latents must share a leading dimension")
     out = torch.empty(N, dtype=F32, device=mu_f.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    _lib.call("mgp_e_log_p_y", mu_f.data_ptr(), var_f.data_ptr(), ptr(mu_a), ptr(var_a), _ld(mu_f), int(stride_s),
-              Y.data_ptr(), None if multiclass_eps is not None else lik_var.data_ptr(), ptr(assign_lik_var),
-              float(multiclass_eps or 0.0), W.data_ptr(), N, K, S, out.data_ptr(), _stream())
+    _lib.call("mgp_e_log_p_y", mu_f, var_f, mu_a, var_a, _ld(mu_f), int(stride_s), Y,
+              None if multiclass_eps is not None else lik_var, assign_lik_var, float(multiclass_eps or 0.0), W, N, K, S,
+              out, _stream())
     return out
 
 
@@ -1225,22 +1101,18 @@ def mixture_predict(mu_f, var_f, mu_a, var_a, lik_var, S=0, Y=None, noise_z=None
     unknown = [w for w in want if w not in MIXTURE_OUTPUTS]
     if unknown:
         raise ValueError(f"unknown outputs {unknown}; choose from {MIXTURE_OUTPUTS}")
-    yp = None
     if Y is not None:
         Y = Y.reshape(-1)
         _check(Y, "Y")
         if Y.numel() != N or not Y.is_contiguous():
             raise ValueError("Y must be contiguous with N elements")
-        yp = Y.data_ptr()
     elif "log_density" in want or "log_density_sum" in want:
         raise ValueError("log_density needs Y")
-    zp = None
     if noise_z is not None:
         _check(noise_z, "noise_z", 3)
         if tuple(noise_z.shape) != (S, N, K):
             raise ValueError("explicit noise must be [S, N, K]")
         noise_z = noise_z.contiguous()
-        zp = noise_z.data_ptr()
     have, out = out or {}, {}
     for name in want:
         shape, dtype = ((N, K) if name == "weights" else (1,) if name == "log_density_sum" else (N,),
@@ -1254,16 +1126,13 @@ def mixture_predict(mu_f, var_f, mu_a, var_a, lik_var, S=0, Y=None, noise_z=None
         else:
             t = torch.empty(shape, dtype=dtype, device=dev)
         out[name] = t
-    wp = wb = None
+    ws_args = [None, 0]   # only the sum needs a workspace
     if "log_density_sum" in out:
-        nbytes = _lib.load().mgp_mixture_predict_workspace_bytes(N, K)
-        if workspace is None or workspace.numel() < nbytes:
-            workspace = _ws(nbytes, dev)
-        wp, wb = workspace.data_ptr(), workspace.numel()
-    ptr = lambda name: out[name].data_ptr() if name in out else None
-    _lib.call("mgp_mixture_predict", mu_f.data_ptr(), var_f.data_ptr(), mu_a.data_ptr(), var_a.data_ptr(), ldf,
-              lik_var.data_ptr(), yp, N, K, int(S), float(jitter), zp, int(seed) & 0xFFFFFFFFFFFFFFFF,
-              int(n_offset), *[ptr(n) for n in MIXTURE_OUTPUTS], wp, wb or 0, _stream())
+        workspace = _workspace("mgp_mixture_predict_workspace_bytes", (N, K), workspace, dev)
+        ws_args = [workspace, workspace.numel()]
+    _lib.call("mgp_mixture_predict", mu_f, var_f, mu_a, var_a, ldf, lik_var, Y, N, K, int(S), float(jitter), noise_z,
+              int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_offset), *[out.get(n) for n in MIXTURE_OUTPUTS], *ws_args,
+              _stream())
     return out
 
 
@@ -1278,8 +1147,8 @@ def mixture_density_grid(mu_f, var_f, lik_var, weights, y_grid):
     weights, y_grid = weights.contiguous(), y_grid.contiguous()
     G = y_grid.numel()
     out = torch.empty(N, G, dtype=F32, device=mu_f.device)
-    _lib.call("mgp_mixture_density_grid", mu_f.data_ptr(), var_f.data_ptr(), _ld(mu_f), lik_var.data_ptr(),
-              weights.data_ptr(), N, K, y_grid.data_ptr(), G, out.data_ptr(), max(G, 1), _stream())
+    _lib.call("mgp_mixture_density_grid", mu_f, var_f, _ld(mu_f), lik_var, weights, N, K, y_grid, G, out, max(G, 1),
+              _stream())
     return out
 
 
@@ -1321,15 +1190,12 @@ def mixture_score(mu_f, var_f, lik_var, weights, Y, want=None, workspace=None, o
         else:
             t = torch.empty(shape, dtype=dtype, device=dev)
         out[name] = t
-    wp = wb = None
+    ws_args = [None, 0]   # only the sum needs a workspace
     if "crps_sum" in out:
-        nbytes = _lib.load().mgp_mixture_score_workspace_bytes(N, K)
-        if workspace is None or workspace.numel() < nbytes:
-            workspace = _ws(nbytes, dev)
-        wp, wb = workspace.data_ptr(), workspace.numel()
-    ptr = lambda name: out[name].data_ptr() if name in out else None
-    _lib.call("mgp_mixture_score", mu_f.data_ptr(), var_f.data_ptr(), _ld(mu_f), lik_var.data_ptr(),
-              weights.data_ptr(), Y.data_ptr(), N, K, *[ptr(n) for n in SCORE_OUTPUTS], wp, wb or 0, _stream())
+        workspace = _workspace("mgp_mixture_score_workspace_bytes", (N, K), workspace, dev)
+        ws_args = [workspace, workspace.numel()]
+    _lib.call("mgp_mixture_score", mu_f, var_f, _ld(mu_f), lik_var, weights, Y, N, K,
+              *[out.get(n) for n in SCORE_OUTPUTS], *ws_args, _stream())
     return out
 
 
@@ -1372,8 +1238,7 @@ def mixture_quantiles(mu_f, var_f, lik_var, weights, levels, out=None):
         return out
     ldq = _ld(out) if N > 1 else Q
     lvd = torch.from_numpy(lv).to(mu_f.device)
-    _lib.call("mgp_mixture_quantiles", mu_f.data_ptr(), var_f.data_ptr(), _ld(mu_f), lik_var.data_ptr(),
-              weights.data_ptr(), N, K, lvd.data_ptr(), Q, out.data_ptr(), ldq, _stream())
+    _lib.call("mgp_mixture_quantiles", mu_f, var_f, _ld(mu_f), lik_var, weights, N, K, lvd, Q, out, ldq, _stream())
     return out
 
 
@@ -1400,16 +1265,12 @@ def vq(obs, code_book, code=None, dist=None):
         raise ValueError("obs and code_book must have the same number of features")
     code = torch.empty(N, dtype=I32, device=obs.device) if code is None else code
     dist = torch.empty(N, dtype=F32, device=obs.device) if dist is None else dist
-    _lib.call("mgp_vq", obs.data_ptr(), ldo, code_book.data_ptr(), ldc, N, k, D, code.data_ptr(), dist.data_ptr(),
-              _stream())
+    _lib.call("mgp_vq", obs, ldo, code_book, ldc, N, k, D, code, dist, _stream())
     return code, dist
 
 
 def kmeans_workspace(N, k, D, R, device):
-    nbytes = _lib.load().mgp_kmeans_workspace_bytes(N, k, D, R)
-    if nbytes == 0:
-        _lib.check("mgp_kmeans_workspace_bytes", 3)
-    return _ws(nbytes, device)
+    return _new_workspace("mgp_kmeans_workspace_bytes", (N, k, D, R), device)
 
 
 def kmeans_init(obs, k, workspace, idx=None, guess=None):
@@ -1417,17 +1278,15 @@ def kmeans_init(obs, k, workspace, idx=None, guess=None):
     guess [k, D] (mgp_kmeans_init)."""
     obs, ldo = _rows(obs, "obs")
     N, D = obs.shape
-    R, gp, ldg, ip = 1, None, 0, None
+    R, ldg = 1, 0
     if guess is not None:
         guess, ldg = _rows(guess, "guess")
-        gp = guess.data_ptr()
     if idx is not None:
         if idx.dtype != torch.int64 or not idx.is_cuda or idx.dim() != 2 or idx.shape[1] != k:
             raise ValueError("idx must be a device int64 tensor [R, k]")
         idx = idx.contiguous()
-        R, ip = idx.shape[0], idx.data_ptr()
-    _lib.call("mgp_kmeans_init", obs.data_ptr(), ldo, N, D, ip, gp, ldg, k, R, workspace.data_ptr(),
-              workspace.numel(), _stream())
+        R = idx.shape[0]
+    _lib.call("mgp_kmeans_init", obs, ldo, N, D, idx, guess, ldg, k, R, workspace, workspace.numel(), _stream())
     return R
 
 
@@ -1436,8 +1295,8 @@ def kmeans_iterate(obs, k, R, B, thresh, workspace, done):
     int32 [R]."""
     obs, ldo = _rows(obs, "obs")
     N, D = obs.shape
-    _lib.call("mgp_kmeans_iterate", obs.data_ptr(), ldo, N, D, k, R, int(B), float(thresh), workspace.data_ptr(),
-              workspace.numel(), done.data_ptr(), _stream())
+    _lib.call("mgp_kmeans_iterate", obs, ldo, N, D, k, R, int(B), float(thresh), workspace, workspace.numel(), done,
+              _stream())
 
 
 def kmeans_select(N, k, D, R, workspace, result):
@@ -1445,8 +1304,7 @@ def kmeans_select(N, k, D, R, workspace, result):
     [float64 distortion | int32 info[4] | pad to 32 B | float32 code_book [k, D]]
     (mgp_kmeans_select), so that one copy brings everything to the host."""
     base = result.data_ptr()
-    _lib.call("mgp_kmeans_select", N, k, D, R, workspace.data_ptr(), workspace.numel(), base + 32, D, base,
-              base + 8, _stream())
+    _lib.call("mgp_kmeans_select", N, k, D, R, workspace, workspace.numel(), base + 32, D, base, base + 8, _stream())
 
 
 def kmeans_update(obs, code, k, workspace=None):
@@ -1461,17 +1319,13 @@ def kmeans_update(obs, code, k, workspace=None):
         workspace = kmeans_workspace(N, k, D, 1, obs.device)
     means = torch.empty(k, D, dtype=F32, device=obs.device)
     counts = torch.empty(k, dtype=I32, device=obs.device)
-    _lib.call("mgp_kmeans_update", obs.data_ptr(), ldo, N, D, code.data_ptr(), k, means.data_ptr(), D,
-              counts.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream())
+    _lib.call("mgp_kmeans_update", obs, ldo, N, D, code, k, means, D, counts, workspace, workspace.numel(), _stream())
     return means, counts
 
 
 # --------------------------------------------------------------------------- greedy variance selection
 def greedy_workspace(N, M, D, device):
-    nbytes = _lib.load().mgp_greedy_workspace_bytes(N, M, D)
-    if nbytes == 0:
-        _lib.check("mgp_greedy_workspace_bytes", 3)
-    return _ws(nbytes, device)
+    return _new_workspace("mgp_greedy_workspace_bytes", (N, M, D), device)
 
 
 def greedy_factor(N, M, device):
@@ -1482,8 +1336,7 @@ def greedy_factor(N, M, device):
 def greedy_init(N, D, variance, threshold, workspace):
     """Start a selection on N points (mgp_greedy_init): d = variance, nothing chosen."""
     _check(variance, "variance")
-    _lib.call("mgp_greedy_init", N, D, variance.data_ptr(), float(threshold), workspace.data_ptr(),
-              workspace.numel(), _stream())
+    _lib.call("mgp_greedy_init", N, D, variance, float(threshold), workspace, workspace.numel(), _stream())
 
 
 def greedy_steps(X, variance, lengthscales, M, B, factor, workspace, state):
@@ -1496,9 +1349,8 @@ def greedy_steps(X, variance, lengthscales, M, B, factor, workspace, state):
         raise ValueError(f"factor must be [M, N] = [{M}, {N}], got {tuple(factor.shape)}")
     if state.dtype != I32 or not state.is_cuda or state.numel() < 2:
         raise ValueError("state must be a device int32 tensor [2]")
-    _lib.call("mgp_greedy_steps", X.data_ptr(), ldx, N, D, variance.data_ptr(), lengthscales.data_ptr(),
-              lengthscales.numel(), M, int(B), factor.data_ptr(), _ld(factor),
-              workspace.data_ptr(), workspace.numel(), state.data_ptr(), _stream())
+    _lib.call("mgp_greedy_steps", X, ldx, N, D, variance, lengthscales, lengthscales.numel(), M, int(B), factor,
+              _ld(factor), workspace, workspace.numel(), state, _stream())
 
 
 def greedy_result(X, M, workspace, residual=True):
@@ -1514,9 +1366,8 @@ def greedy_result(X, M, workspace, residual=True):
     trace = torch.empty(M, dtype=torch.float64, device=dev)
     res = torch.empty(N, dtype=torch.float64, device=dev) if residual else None
     info = torch.empty(2, dtype=I32, device=dev)
-    _lib.call("mgp_greedy_result", X.data_ptr(), ldx, N, D, M, workspace.data_ptr(), workspace.numel(),
-              indices.data_ptr(), Z.data_ptr(), D, dmax.data_ptr(), trace.data_ptr(),
-              res.data_ptr() if residual else None, info.data_ptr(), _stream())
+    _lib.call("mgp_greedy_result", X, ldx, N, D, M, workspace, workspace.numel(), indices, Z, D, dmax, trace,
+              res, info, _stream())
     return indices, Z, dmax, trace, res, info
 
 
@@ -1553,7 +1404,6 @@ def path_eval(X, Omega, phase, W, A=None, out=None):
         out = padded(C, N, X.device)
     elif tuple(out.shape) != (C, N):
         raise ValueError(f"out must be [{C}, {N}]")
-    _lib.call("mgp_path_eval", X.data_ptr(), ldx, N, D, Omega.data_ptr(), ldo, phase.data_ptr(), R,
-              A.data_ptr() if A is not None else None, _ld(A) if A is not None else 0, M, W.data_ptr(), _ld(W), C,
-              out.data_ptr(), _ld(out), _stream())
+    _lib.call("mgp_path_eval", X, ldx, N, D, Omega, ldo, phase, R, A, _ld(A) if A is not None else 0, M, W, _ld(W), C,
+              out, _ld(out), _stream())
     return out

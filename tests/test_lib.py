@@ -21,8 +21,173 @@ def test_exports_every_header_symbol():
     assert not missing, missing
 
 
-def test_binding_table_matches_header():
-    assert sorted(_lib.SIGNATURES) == _lib.header_symbols()
+C = ctypes
+SMALL_HEADER = """
+#ifndef SMALL_H
+#define SMALL_H
+#define mgp_macro(x) int mgp_from_define(int x);
+#define mgp_long_macro(x) \\
+  int mgp_from_continued_define(int x);
+typedef void* mgp_stream_t; /* hipStream_t */
+enum { MGP_OK = 0 };
+/* int mgp_in_block_comment(int a);
+   spread over lines */
+// int mgp_after_slashes(int a);
+const char* mgp_name(void);
+void* mgp_handle();   // int mgp_trailing_comment(void);
+size_t mgp_bytes(int a, int32_t b, int64_t c, uint64_t d, size_t e, float f, double g, mgp_stream_t s);
+int mgp_broken(const float* const* Z, /* int mgp_inner(int a); */
+               const int32_t *n_ls,
+               float* out, int64_t ldo);
+float* mgp_float_ptr(void* img, int64_t M);
+int64_t mgp_unnamed(int64_t, const double*);
+#endif
+"""
+
+
+def test_parser_reads_every_declaration_form():
+    """Scalars by exact width, every pointer spelling as c_void_p, the three return kinds,
+    (void) / (), a declaration over three lines; nothing from comments or #define lines."""
+    table = _lib.parse_prototypes(SMALL_HEADER)
+    assert table == {
+        "mgp_name": (C.c_char_p, []),
+        "mgp_handle": (C.c_void_p, []),
+        "mgp_bytes": (C.c_size_t, [C.c_int, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t, C.c_float, C.c_double,
+                                   C.c_void_p]),
+        "mgp_broken": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+        "mgp_float_ptr": (C.c_void_p, [C.c_void_p, C.c_int64]),
+        "mgp_unnamed": (C.c_int64, [C.c_int64, C.c_void_p]),
+    }
+    assert list(table) == ["mgp_name", "mgp_handle", "mgp_bytes", "mgp_broken", "mgp_float_ptr", "mgp_unnamed"]
+    for _, args in table.values():
+        assert all(a is C.c_void_p or a in (C.c_int, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t, C.c_float,
+                                            C.c_double) for a in args)
+
+
+@pytest.mark.parametrize("decl, named", [
+    ("int mgp_bad(long n);", "mgp_bad"),
+    ("int mgp_bad(int64_t M, struct foo v);", "struct foo v"),
+    ("int mgp_bad(unsigned int n);", "unsigned int n"),
+    ("long mgp_bad(void);", "mgp_bad"),
+    ("unsigned mgp_bad(void);", "mgp_bad"),
+    ("int mgp_bad(int32_t a, short b);", "parameter 2"),
+])
+def test_parser_refuses_types_outside_the_vocabulary(decl, named):
+    with pytest.raises(_lib.MGPLibraryError, match="mgp_bad") as e:
+        _lib.parse_prototypes("int mgp_fine(int a);\n" + decl)
+    assert named in str(e.value)
+
+
+@pytest.mark.parametrize("decl", [
+    "int mgp_cb(int (*fn)(int), int64_t n);",
+    "int mgp_attr(int a) __attribute__((deprecated));",
+    "int mgp_open(int a;",
+])
+def test_parser_refuses_a_declaration_it_cannot_read(decl):
+    """An entry the pattern misses would get no argtypes and ctypes' default int conversion."""
+    with pytest.raises(_lib.MGPLibraryError, match="cannot parse"):
+        _lib.parse_prototypes("int mgp_fine(int a);\n" + decl + "\nint mgp_after(void);")
+
+
+def test_header_symbols_and_missing_header(tmp_path):
+    h = tmp_path / "small.h"
+    h.write_text(SMALL_HEADER)
+    assert _lib.header_symbols(str(h)) == sorted(
+        ["mgp_name", "mgp_handle", "mgp_bytes", "mgp_broken", "mgp_float_ptr", "mgp_unnamed"])
+    with pytest.raises(_lib.MGPLibraryError, match="absent.h"):
+        _lib.header_symbols(str(tmp_path / "absent.h"))
+
+
+def test_prototypes_of_the_real_header_are_pinned():
+    """Exact restype and argtypes of entries that carry each width the ABI uses."""
+    P, I32, I64, U64, SZ, F, D = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t, C.c_float, C.c_double
+    S = _lib.SIGNATURES
+    assert len(S) >= 115 and sorted(S) == _lib.header_symbols()
+    assert S["mgp_version"] == (C.c_char_p, [])
+    assert S["mgp_status_string"] == (C.c_char_p, [C.c_int])
+    assert S["mgp_chol_workspace_bytes"] == (SZ, [I64, I32])
+    assert S["mgp_x6_bound_ptr"] == (P, [P, I64, I64, I32])
+    assert S["mgp_kl_grad"] == (C.c_int, [P, I64, P, I64, I64, I64, I32, D, P, I64, P, I64, I64, P])
+    assert S["mgp_elbo_terms"] == (C.c_int, [P, P, P, P, I64, P, P, I64, I32, I32, F, F, P, P, U64, I64, P, P, SZ, P])
+    assert S["mgp_kuu_potrf_trtri"] == (C.c_int, [P, I64, I64, I32, P, P, P, F, I32, P, P, I64, I64, P, P, SZ, P])
+    lib = _lib.load()
+    for name, (res, args) in S.items():
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+
+
+class _FakeTensor:
+    def __init__(self, ptr):
+        self.ptr = ptr
+
+    def data_ptr(self):
+        return self.ptr
+
+
+def test_marshal_converts_tensors_and_lists_only():
+    import torch
+    t = torch.zeros(4, 4)
+    assert _lib.marshal(t) == t.data_ptr() and isinstance(_lib.marshal(t), int)
+    assert _lib.marshal(_FakeTensor(4096)) == 4096
+    u = torch.ones(3)
+    for seq in ([t, None, u], (t, None, u)):
+        arr = _lib.marshal(seq)
+        assert isinstance(arr, C.c_void_p * 3)
+        assert list(arr) == [t.data_ptr(), None, u.data_ptr()]
+    assert len(_lib.marshal([])) == 0
+    ready = (C.c_void_p * 2)(8, None)
+    lengths = (C.c_int64 * 2)(4, 4)
+    assert _lib.marshal(ready) is ready and _lib.marshal(lengths) is lengths
+    handle = C.c_void_p(8)
+    assert _lib.marshal(handle) is handle
+    for v in (3, -1, 1 << 40, 0.25, None, True):
+        assert _lib.marshal(v) is v
+
+
+def test_call_marshals_lists_and_prebuilt_arrays_alike():
+    """mgp_adam_step_set with all-empty blocks (rows = 0) is a no-op that needs no GPU
+    (csrc/train.hip): the same call with the pointer arrays as lists of CPU tensors and as
+    prebuilt ctypes arrays returns normally."""
+    import torch
+    n = 2
+    theta, u, g, m1, m2 = ([torch.zeros(4, 4) for _ in range(n)] for _ in range(5))
+    I64, I32 = C.c_int64 * n, C.c_int32 * n
+    empty, four, f32 = I64(0, 0), I64(4, 4), I32(0, 0)
+    hyper = (1e-3, 0.9, 0.999, 1e-7, 1, -1.0, None)   # lr, beta1, beta2, eps, t, grad_sign, stream
+    assert _lib.call("mgp_adam_step_set", n, theta, [None, u[1]], g, f32, four, m1, m2, empty, four, four,
+                     *hyper) is None
+    at, au, ag, am1, am2 = (_lib.marshal(ts) for ts in (theta, u, g, m1, m2))
+    assert _lib.call("mgp_adam_step_set", n, at, au, ag, f32, four, am1, am2, empty, four, four, *hyper) is None
+    # with rows > 0 the same lists reach the size checks (ld < cols), still before any HIP call
+    with pytest.raises(_lib.MGPError) as e:
+        _lib.call("mgp_adam_step_set", n, theta, u, g, f32, four, m1, m2, four, four, I64(4, 3), *hyper)
+    assert e.value.status == -11
+
+
+def test_call_raw_takes_converted_arguments_only():
+    """call_raw is call without the marshalling pass: the same no-op with prebuilt arrays,
+    and a tensor is refused by ctypes instead of being converted."""
+    import torch
+    n = 1
+    arr = [_lib.marshal([torch.zeros(4, 4)]) for _ in range(5)]
+    one = (C.c_int64 * n)(4)
+    tail = ((C.c_int64 * n)(0), one, one, 1e-3, 0.9, 0.999, 1e-7, 1, -1.0, None)
+    assert _lib.call_raw("mgp_adam_step_set", n, arr[0], arr[1], arr[2], (C.c_int32 * n)(0), one, arr[3], arr[4],
+                         *tail) is None
+    with pytest.raises(C.ArgumentError):
+        _lib.call_raw("mgp_adam_step_set", n, torch.zeros(4, 4), arr[1], arr[2], (C.c_int32 * n)(0), one, arr[3],
+                      arr[4], *tail)
+    with pytest.raises(_lib.MGPError) as e:
+        _lib.call_raw("mgp_rbf_kuf", None, 1, None, 1, 10, 10, 1, None, None, 1, None, 12, None)
+    assert e.value.status == -1
+
+
+def test_refused_call_raises_mgp_error():
+    import torch
+    Z = torch.zeros(10, 1)
+    with pytest.raises(_lib.MGPError) as e:
+        _lib.call("mgp_rbf_kuf", None, 1, Z, 1, 10, 10, 1, None, None, 1, None, 12, None)
+    assert e.value.status == -1
 
 
 def test_status_strings_and_argument_checks():
@@ -60,18 +225,6 @@ def test_product_path_fails_loudly_without_library(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "missing.so"))
     with pytest.raises(_lib.MGPLibraryError):
         _lib.load()
-
-
-def test_binding_arities_match_header():
-    """Each ctypes prototype has as many arguments as the header declaration."""
-    import re
-    text = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER_PATH).read(), flags=re.S)
-    for name, (_, args) in _lib.SIGNATURES.items():
-        m = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", text, re.S)
-        assert m, name
-        decl = m.group(1).strip()
-        n = 0 if decl in ("", "void") else decl.count(",") + 1
-        assert n == len(args), (name, n, len(args))
 
 
 def test_jitter_argument_is_validated():
@@ -185,3 +338,25 @@ def test_conditional_backward_prep_entries_check_arguments():
         c, 1 << 30, c, 128, c, M, M * M, c, K, c, M, c, c, 128, M, N, K, c, K, c, M, M * M, c, 128, c, M, c, c, wsb,
         cfr, 1 << 30, c, c, pr, nb, None, None)
     assert cb(cfr=None) == -30 and cb(pr=None) == -33 and cb(nb=pb - 1) == -34
+
+
+def test_workspace_helpers_size_reuse_and_refuse():
+    """ops._workspace keeps a buffer that is large enough and replaces one that is not
+    (count scales the size for the batch entries); the *_workspace functions whose entry
+    answers 0 bytes refuse the sizes with MGP_ERR_UNSUPPORTED.  Host memory: no GPU."""
+    import torch
+    from modulatedgps_amd import ops
+    lib = _lib.load()
+    entry = "mgp_chol_backward_workspace_bytes"
+    nbytes = lib.mgp_chol_backward_workspace_bytes(64)
+    ws = ops._workspace(entry, (64,), None, "cpu")
+    assert ws.dtype == torch.uint8 and ws.numel() == nbytes > 16
+    assert ops._workspace(entry, (64,), ws, "cpu") is ws
+    both = ops._workspace(entry, (64,), ws, "cpu", count=2)
+    assert both is not ws and both.numel() == 2 * nbytes
+    assert ops._workspace(entry, (64,), both, "cpu") is both
+    assert ops.natgrad_workspace(64, 3, "cpu").numel() == lib.mgp_natgrad_workspace_bytes(64, 3)
+    with pytest.raises(_lib.MGPError) as e:
+        ops.natgrad_workspace(0, 3, "cpu")
+    assert e.value.status == 3 and "mgp_natgrad_workspace_bytes" in str(e.value)
+    assert ops.full_cov_workspace_bytes(64, 100, 3) == lib.mgp_full_cov_workspace_bytes(64, 100, 3)
