@@ -29,7 +29,7 @@
  *    written; each entry's comment repeats its own):
  *      input dimension D <= 32: mgp_rbf_kuf, mgp_rbf_kuu (mgp_rbf_kuu_jitter),
  *        mgp_rbf_kuf_x6 / _f16, the Kuf side job of mgp_kuu_potrf_trtri_kuf,
- *        mgp_rbf_backward / _batch, mgp_full_cov_conditional, mgp_path_eval, mgp_vq, mgp_kmeans_*
+ *        mgp_rbf_backward / _batch, every mgp_matern_* entry, mgp_full_cov_conditional, mgp_path_eval, mgp_vq, mgp_kmeans_*
  *        (these also N <= 2^31 - 1, k <= N and R <= 64 runs), mgp_greedy_* (also N <= 2^31 - 1
  *        and M <= N);
  *      D unbounded: mgp_kuu_potrf_trtri / _ev / _ex (a generic Kuu build above D = 32);
@@ -589,6 +589,66 @@ int mgp_rbf_backward_batch(int32_t batch, const float* X, int64_t ldx, int64_t N
                            int64_t ldgf, const float* const* gKuu, int64_t ldgu, int32_t accumulate,
                            float* const* gZ, int64_t ldgz, double* const* g_var, double* const* g_ls,
                            void* workspace, size_t workspace_bytes, mgp_stream_t stream);
+
+/* ---------------------------------------------------------------- Matern kernels (csrc/matern.hip)
+ * Matern-3/2 and Matern-5/2 beside the SquaredExponential entries above (GPflow Matern32 /
+ * Matern52 in place of SquaredExponential at models.py:135, 139).  nu2 = 2 nu is 3 or 5:
+ *   s = sqrt(nu2) sqrt(sum_d ((Z[m,d] - X[n,d]) / ls[d])^2)
+ *   nu2 = 3: k = var (1 + s) exp(-s)        nu2 = 5: k = var (1 + s + s^2 / 3) exp(-s)
+ * Numerics: the direct form -- each z_d - x_d is formed on the raw float32 coordinates first,
+ * then scaled by sqrt(nu2) / l_d, squared and summed; no expanded form, no reference point.  So
+ * K(Z + c, X + c) = K(Z, X) bit for bit whenever the shifted coordinates are exact (the
+ * translation contract of the RBF entries), and mgp_matern_kuu is bitwise symmetric.
+ * Conventions as the RBF entries': n_ls = 1 or D, hyper-parameters are device pointers, nothing
+ * is allocated, every argument is checked before any pointer is read or HIP call made.
+ * D <= 32 (D > 32: MGP_ERR_UNSUPPORTED).  N <= 0 or M <= 0: MGP_OK after the checks, nothing
+ * done (mgp_matern_backward then leaves its outputs as they are).
+ *
+ * mgp_matern_kuf: Kuf [M][ldk] float32 (ldk % 4 == 0, 16-B aligned), as mgp_rbf_kuf.
+ *   -1 .. -13: X, ldx, Z, ldz, N, M, D, variance, lengthscales, n_ls, nu2, Kuf, ldk.
+ * mgp_matern_kuu: Kuu [M][ldk] float32 = K(Z, Z) + jitter on the diagonal, as mgp_rbf_kuu.
+ *   -1 .. -11: Z, ldz, M, D, variance, lengthscales, n_ls, nu2, jitter, Kuu, ldk. */
+int mgp_matern_kuf(const float* X, int64_t ldx, const float* Z, int64_t ldz, int64_t N, int64_t M,
+                   int32_t D, const float* variance, const float* lengthscales, int32_t n_ls, int32_t nu2,
+                   float* Kuf, int64_t ldk, mgp_stream_t stream);
+int mgp_matern_kuu(const float* Z, int64_t ldz, int64_t M, int32_t D, const float* variance,
+                   const float* lengthscales, int32_t n_ls, int32_t nu2, float jitter, float* Kuu, int64_t ldk,
+                   mgp_stream_t stream);
+/* K1 for Matern: the Kuf fragment image written directly (no f32 Kuf), for K4 (mgp_trsm_stats_x6 /
+ * _f16 / _f16x8 / _x6_f16) unchanged.  kfr_format 0: split-bf16 "x6" (what mgp_rbf_kuf_x6 writes),
+ * 1: split-f16 (mgp_rbf_kuf_f16), as kfr_format of mgp_kuu_potrf_trtri_kuf.  Kfr: at least
+ * mgp_x6_cols_bytes(M, N) bytes, 16-B aligned.  Rows >= M and columns >= N of the padded image are
+ * zeros; the trailer's float 0 is the variance (Kuf <= variance: the split-f16 scale bound) and its
+ * floats [32, 64) are zeros.
+ *   -1 .. -14: X, ldx, Z, ldz, N, M, D, variance, lengthscales, n_ls, nu2, Kfr, kfr_bytes, kfr_format. */
+int mgp_matern_kuf_image(const float* X, int64_t ldx, const float* Z, int64_t ldz, int64_t N, int64_t M,
+                         int32_t D, const float* variance, const float* lengthscales, int32_t n_ls, int32_t nu2,
+                         void* Kfr, size_t kfr_bytes, int32_t kfr_format, mgp_stream_t stream);
+/* One layer's Kuu = K(Z, Z) + jitter I built in float64 (differences of the float32 inputs,
+ * scaling, sqrt and exp in double) into the workspace, then factorised by K3's float64-input
+ * path: L (nullable) and LinvT = (L^-1)^T rounded to float32 ([M][ldl], ldl % 4 == 0, 16-B
+ * aligned), info as mgp_potrf_trtri.  Workspace: mgp_matern_chol_workspace_bytes(M) (0 for
+ * M <= 0), 16-B aligned.
+ *   -1 .. -15: Z, ldz, M, D, variance, lengthscales, n_ls, nu2, jitter, L, LinvT, ldl, info,
+ *   workspace, workspace_bytes (the last two: MGP_ERR_WORKSPACE). */
+size_t mgp_matern_chol_workspace_bytes(int64_t M);
+int mgp_matern_kuu_potrf_trtri(const float* Z, int64_t ldz, int64_t M, int32_t D, const float* variance,
+                               const float* lengthscales, int32_t n_ls, int32_t nu2, float jitter, float* L,
+                               float* LinvT, int64_t ldl, int32_t* info, void* workspace, size_t workspace_bytes,
+                               mgp_stream_t stream);
+/* Reverse mode of the Matern K(Z, X): arguments and semantics of mgp_rbf_backward with nu2 after
+ * n_ls (symmetric, accumulate; gZ float, g_var and g_ls device doubles).  Nothing divides by s:
+ * coincident points contribute exact zeros to gZ and g_ls.  Fixed summation orders, float64
+ * partial sums, no atomics: two calls return the same bits.
+ * Workspace: mgp_matern_backward_workspace_bytes(N, M, D) (0 outside N >= 0, M >= 1, 1 <= D <= 32).
+ *   -1 .. -19: X, ldx, Z, ldz, N, M, D, variance, lengthscales, n_ls, nu2, gK, ldg, symmetric,
+ *   accumulate, gZ, ldgz, g_var, g_ls. */
+size_t mgp_matern_backward_workspace_bytes(int64_t N, int64_t M, int32_t D);
+int mgp_matern_backward(const float* X, int64_t ldx, const float* Z, int64_t ldz, int64_t N, int64_t M,
+                        int32_t D, const float* variance, const float* lengthscales, int32_t n_ls, int32_t nu2,
+                        const float* gK, int64_t ldg, int32_t symmetric, int32_t accumulate, float* gZ,
+                        int64_t ldgz, double* g_var, double* g_ls, void* workspace, size_t workspace_bytes,
+                        mgp_stream_t stream);
 
 /* ---------------------------------------------------------------- K7
  * Whitened Gaussian KL (GPflow gauss_kl(q_mu, q_sqrt, K=None), reached through

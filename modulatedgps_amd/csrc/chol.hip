@@ -1604,9 +1604,18 @@ extern "C" int mgp_potrf_trtri(const float* A, int64_t lda, int64_t strideA, int
 int mgp::mgp_potrf_trtri_f64(const double* Ad, int64_t ldad, int64_t strideAd, int64_t M, int batch, float* LinvT,
                              int64_t ldl, int64_t strideL, int32_t* info, void* workspace, size_t workspace_bytes,
                              hipStream_t s) {
+  return mgp_potrf_trtri_f64_l(Ad, ldad, strideAd, M, batch, nullptr, LinvT, ldl, strideL, info, workspace,
+                               workspace_bytes, s);
+}
+
+// The same with L (nullable) written too, in LinvT's layout (matern.hip): chol_prep_f64 and the
+// step launches already handle a.L.
+int mgp::mgp_potrf_trtri_f64_l(const double* Ad, int64_t ldad, int64_t strideAd, int64_t M, int batch, float* L,
+                               float* LinvT, int64_t ldl, int64_t strideL, int32_t* info, void* workspace,
+                               size_t workspace_bytes, hipStream_t s) {
   if (batch < 1 || batch > kMaxBatch || M < 1) return MGP_ERR_UNSUPPORTED;
   CholArgs a = {};
-  a.LinvT = LinvT; a.ldl = ldl; a.strideL = strideL;
+  a.L = L; a.LinvT = LinvT; a.ldl = ldl; a.strideL = strideL;
   a.info = info; a.M = M;
   return chol_run(a, batch, workspace, workspace_bytes, s, nullptr, nullptr, Ad, ldad, strideAd);
 }

@@ -58,6 +58,10 @@ int gram_f16_rowscaled(const float* X, int64_t ldx, int64_t MI, const float* Y, 
 int mgp_potrf_trtri_f64(const double* Ad, int64_t ldad, int64_t strideAd, int64_t M, int batch, float* LinvT,
                         int64_t ldl, int64_t strideL, int32_t* info, void* workspace, size_t workspace_bytes,
                         hipStream_t s);
+// The same, also writing L_b = chol(A_b) (nullable; LinvT's layout) rounded to float32.
+int mgp_potrf_trtri_f64_l(const double* Ad, int64_t ldad, int64_t strideAd, int64_t M, int batch, float* L,
+                          float* LinvT, int64_t ldl, int64_t strideL, int32_t* info, void* workspace,
+                          size_t workspace_bytes, hipStream_t s);
 
 // ------------------------------------------------------------------ MFMA
 // D(32x32) += A(32x2) * B(2x32), exact f32 (fmaf chain).  Lane l supplies

@@ -18,6 +18,10 @@ arguments and method names).  The SMGP ELBO hot path
      mgp_trsm_stats_x6, mgp_expert_conditional_x6 -- csrc/images.hip, csrc/trsm_stats.hip, csrc/expert_cond.hip;
      config.set_conditional_mode("f32"): mgp_rbf_kuf + mgp_trsm_stats +
      mgp_expert_conditional_f32 on the exact-f32 MFMA)
+    (a layer on a Matern32 / Matern52 kernel: mgp_matern_kuu_potrf_trtri and
+     mgp_matern_kuf_image per layer, through the kernel's factorise / kuf_image / backward
+     methods, then the same split, K4 and K5 launches; the two-layer and fused launches above
+     run only where both kernels are SquaredExponential)
   K6 mgp_elbo_terms         sum_n lse_s(...)        models.py:55-67,73-76
   mgp_elbo_combine          ELBO scalar             models.py:76,79
 
@@ -67,10 +71,22 @@ _T_BOUND = True   # the C-images backward takes max |LinvT| from K3's bounded L^
 # S_k = L_k L_k^T.  C_IMAGES_MAX_BYTES (per layer), when set, overrides it.
 C_IMAGES_HBM_FRACTION = 0.4
 C_IMAGES_MAX_BYTES = None
-from .kernels import SquaredExponential
+from .kernels import Matern32, Matern52, SquaredExponential
 from .likelihoods import MultiClass
 
 TAU = 1e-2  # RelaxedOneHotCategorical temperature, models.py:60
+
+
+def _is_se(kernel):
+    return isinstance(kernel, SquaredExponential)
+
+
+def _matern_unsupported(kernel, what):
+    """Surfaces that are SquaredExponential-only (spectral features, the Knn of the full
+    covariance) refuse a Matern kernel before anything is launched."""
+    if not _is_se(kernel):
+        raise NotImplementedError(f"{what} is not implemented for a {type(kernel).__name__} kernel "
+                                  "(SquaredExponential only)")
 
 
 def _splitmix64(x):
@@ -136,8 +152,8 @@ class SVGPModified:
             raise NotImplementedError("q_diag=True is not used by the reference models")
         if mean_function is not None:
             raise NotImplementedError("the reference layers use the Zero mean function")
-        if not isinstance(kernel, SquaredExponential):
-            raise TypeError("kernel must be modulatedgps_amd.kernels.SquaredExponential")
+        if not isinstance(kernel, (SquaredExponential, Matern32, Matern52)):
+            raise TypeError("kernel must be a modulatedgps_amd.kernels SquaredExponential, Matern32 or Matern52")
         self.device = torch.device(device or kernel.device or default_device())
         self.kernel = kernel
         self.likelihood = likelihood
@@ -182,13 +198,15 @@ class SVGPModified:
 
     # ------------------------------------------------------------------ ops
     def Kuu(self, out=None):
+        if not _is_se(self.kernel):
+            return ops.matern_kuu(self.Z, self.kernel.variance, self.kernel.lengthscales, self.kernel.nu2,
+                                  default_jitter(), out=out)
         return ops.rbf_kuu(self.Z, self.kernel.variance, self.kernel.lengthscales, default_jitter(),
                            out=out)
 
     def factorise(self, want_L=False):
         """Kuu (float64) -> L, (L^-1)^T (float32 [1, M, M]) and info (models.py:135,141)."""
-        return ops.kuu_potrf_trtri([self.Z], [self.kernel.variance], [self.kernel.lengthscales],
-                                   default_jitter(), want_L=want_L)
+        return self.kernel.factorise(self.Z, want_L=want_L)
 
     def prior_kl(self, out=None):
         """GPflow SVGP.prior_kl -> gauss_kl(q_mu, q_sqrt) whitened (models.py:79); float64 [1]."""
@@ -201,8 +219,7 @@ class SVGPModified:
         bufs = bufs or {}
         X = self.kernel._x(X)
         with _Stage(timing, "rbf_kuf"):
-            Kfr = ops.rbf_kuf_x6(X, self.Z, self.kernel.variance, self.kernel.lengthscales,
-                                 out=bufs.get("Kfr"), fmt=fmt)
+            Kfr = self.kernel.kuf_image(X, self.Z, out=bufs.get("Kfr"), fmt=fmt)
         with _Stage(timing, "split_tri"):
             Lfr = ops.split_lower_x6(self.q_sqrt, out=bufs.get("Lfr"), fmt=fmt)
         return Kfr, Lfr
@@ -225,8 +242,12 @@ class SVGPModified:
             Kfr, Lfr = images if images is not None else self.operand_images(X, bufs, timing, fmt)
         else:
             with _Stage(timing, "rbf_kuf"):
-                Kuf = ops.rbf_kuf(X, self.Z, self.kernel.variance, self.kernel.lengthscales,
-                                  out=bufs.get("Kuf"))
+                if _is_se(self.kernel):
+                    Kuf = ops.rbf_kuf(X, self.Z, self.kernel.variance, self.kernel.lengthscales,
+                                      out=bufs.get("Kuf"))
+                else:
+                    Kuf = ops.matern_kuf(X, self.Z, self.kernel.variance, self.kernel.lengthscales,
+                                         self.kernel.nu2, out=bufs.get("Kuf"))
         if conditional_mode() == "f32":
             with _Stage(timing, "trsm_stats"):
                 A, stats = ops.trsm_stats(LinvT, Kuf, self.q_mu, A=bufs.get("A"),
@@ -275,7 +296,7 @@ class SVGPModified:
             self._last_info = info
             LinvT = LinvT[0]
         fmt = forward_image_format()
-        Kfr = ops.rbf_kuf_x6(X, self.Z, self.kernel.variance, self.kernel.lengthscales, fmt=fmt)
+        Kfr = self.kernel.kuf_image(X, self.Z, fmt=fmt)
         Tfr = ops.split_upper_x6(LinvT, fmt=fmt)
         Afr, stats = ops.trsm_stats_x6(Tfr, Kfr, self.q_mu[:, k0:k1], M, N,
                                        f16_variance=self.kernel.variance if fmt == "f16" else None, in_fmt=fmt)
@@ -369,6 +390,7 @@ class SVGPModified:
         Leading dimensions are batch: each leading index has its own N x N blocks.  Tiled
         copies of one input (recognised as in _marginals_kn, or tiled=True) are computed
         once and returned as expand() views; distinct leading slices are computed in turn."""
+        _matern_unsupported(self.kernel, "predict_f(full_cov=True)")
         if not isinstance(Xnew, torch.Tensor):
             Xnew = torch.as_tensor(np.asarray(Xnew))
         if Xnew.dim() <= 2:
@@ -427,6 +449,8 @@ class SVGPModified:
         factorisation raises MGPLinAlgError, and the caller passes a larger jitter."""
         if full_output_cov:
             raise NotImplementedError("full_output_cov predictions are not implemented")
+        if full_cov:
+            _matern_unsupported(self.kernel, "predict_f_samples(full_cov=True)")
         jitter = default_jitter() if jitter is None else float(jitter)
         mean, var = self.predict_f(Xnew, full_cov=full_cov, tiled=tiled)
         lead, (N, K) = tuple(mean.shape[:-2]), mean.shape[-2:]
@@ -460,6 +484,7 @@ class SVGPModified:
         Philox draws keyed by `seed`, or by a fresh key of the layer.  1024 features is a
         convention, not a measured optimum.  ValueError on bad arguments before anything is
         uploaded."""
+        _matern_unsupported(self.kernel, "sample_paths")
         from .paths import LayerPaths
         return LayerPaths(self, num_samples, num_features, seed=seed, basis=basis, noise=noise)
 
@@ -675,7 +700,8 @@ class SMGP(SGP):
                 b["Afr_" + L] = torch.empty(ops.x6_cols_bytes(Mx, N), dtype=torch.uint8, device=dev)
                 b["Tfr_" + L] = torch.empty(ops.x6_lower_bytes(Mx, 1), dtype=torch.uint8, device=dev)
         b["x6"] = x6
-        if Mf == Ma and self.pred_layer.Z.shape[1] == self.assign_layer.Z.shape[1]:
+        if Mf == Ma and self.pred_layer.Z.shape[1] == self.assign_layer.Z.shape[1] and self._both_se():
+            # (the two-layer K3 builds SquaredExponential Kuu; a Matern layer factorises on its own)
             b["LinvT2"] = ops.padded(Mf, Mf, dev, batch=2)
         b["train"] = bool(train)
         if train:
@@ -738,6 +764,11 @@ class SMGP(SGP):
         if prep_event is not None:
             prep_event.record()
         return outs[0], outs[1]
+
+    def _both_se(self):
+        """Both layers on SquaredExponential kernels: what the two-layer and fused launches
+        (batched K3 with K1 as its side job, bounded L^-T split, mgp_rbf_backward_batch) compute."""
+        return _is_se(self.pred_layer.kernel) and _is_se(self.assign_layer.kernel)
 
     def _prep_event(self):
         """The K3 prep-done event (created once: its handle is passed to the C-ABI)."""
@@ -811,8 +842,7 @@ class SMGP(SGP):
                     X_ = layer.kernel._x(X)
                     if L not in late and not k1_in_k3:
                         with _Stage(timing, "rbf_kuf"):
-                            ops.rbf_kuf_x6(X_, layer.Z, layer.kernel.variance, layer.kernel.lengthscales,
-                                           out=b["Kfr_" + L], fmt=fmt)
+                            layer.kernel.kuf_image(X_, layer.Z, out=b["Kfr_" + L], fmt=fmt)
                     with _Stage(timing, "split_tri"):
                         if not q_batch:
                             ops.split_lower_x6(layer.q_sqrt, out=b["Lfr_" + L], fmt=fmt)
@@ -857,8 +887,7 @@ class SMGP(SGP):
             def kuf_late(L):   # a K1 kept off the chain's window (schedules k1a_late, k1_main, serial)
                 layer = self.pred_layer if L == "f" else self.assign_layer
                 with _Stage(timing, "rbf_kuf"):
-                    ops.rbf_kuf_x6(layer.kernel._x(X), layer.Z, layer.kernel.variance, layer.kernel.lengthscales,
-                                   out=b["Kfr_" + L], fmt=fmt)
+                    layer.kernel.kuf_image(layer.kernel._x(X), layer.Z, out=b["Kfr_" + L], fmt=fmt)
         LinvT = {"f": LinvT_f, "a": LinvT_a}
         bufs = {L: {"Kuf": b["Kuf_" + L], "A": b["A_" + L], "stats": b["stats_" + L],
                     "fmean": b["mu_" + L], "fvar": b["var_" + L], "ws_expert": b["ws_expert"],
@@ -1071,7 +1100,8 @@ class SMGP(SGP):
         """Both layers' Cholesky / RBF backward can share launches: same M, D and
         lengthscale count (mgp_chol_backward_batch, mgp_rbf_backward_batch)."""
         f, a = self.pred_layer, self.assign_layer
-        return (f.Z.shape == a.Z.shape and f.kernel.lengthscales.numel() == a.kernel.lengthscales.numel()
+        return (self._both_se() and f.Z.shape == a.Z.shape
+                and f.kernel.lengthscales.numel() == a.kernel.lengthscales.numel()
                 and f.Z.stride() == a.Z.stride())
 
     def elbo_and_grad(self, X, Y, noise=None, seed=None, n_offset=0, n_total=None, process_group=None,
@@ -1128,13 +1158,11 @@ class SMGP(SGP):
                 gKuu = ops.chol_backward(b["L_" + L], b["LinvT_" + L], g["g_Lm"])
             with _Stage(timing, "rbf_bwd"):
                 k = layer.kernel
-                gZ, gvar, gls = ops.rbf_backward(X, layer.Z, k.variance, k.lengthscales, g["g_Kuf"],
-                                                 accumulate=True, g_var=g["g_var"],
-                                                 gZ=torch.zeros_like(layer.Z),
-                                                 g_ls=torch.zeros(k.lengthscales.numel(), dtype=torch.float64,
-                                                                  device=self.device))
-                ops.rbf_backward(layer.Z, layer.Z, k.variance, k.lengthscales, gKuu, symmetric=True,
-                                 accumulate=True, gZ=gZ, g_var=gvar, g_ls=gls)
+                gZ, gvar, gls = k.backward(X, layer.Z, g["g_Kuf"], accumulate=True, g_var=g["g_var"],
+                                           gZ=torch.zeros_like(layer.Z),
+                                           g_ls=torch.zeros(k.lengthscales.numel(), dtype=torch.float64,
+                                                            device=self.device))
+                k.backward(layer.Z, layer.Z, gKuu, symmetric=True, accumulate=True, gZ=gZ, g_var=gvar, g_ls=gls)
             return {name + ".Z": gZ, name + ".variance": gvar, name + ".lengthscales": gls,
                     name + ".q_mu": g["g_q_mu"], name + ".q_sqrt": g["g_q_sqrt"]}
 
@@ -1438,6 +1466,8 @@ class SMGP(SGP):
         predict_mean(X) = sum_k weights f [S, N] evaluate them at any X.  The relaxed-one-hot
         sampling of W at tau = 1e-2 is left out: it is discontinuous in the logits.  A
         MultiClass pred likelihood raises NotImplementedError from predict_mean."""
+        for layer in (self.pred_layer, self.assign_layer):
+            _matern_unsupported(layer.kernel, "sample_paths")
         from .paths import MixturePaths
         return MixturePaths(self, num_samples, num_features, seed=seed)
 

@@ -582,6 +582,92 @@ def rbf_backward(X, Z, variance, lengthscales, gK, symmetric=False, accumulate=F
     return gZ, g_var, g_ls
 
 
+# --------------------------------------------------------------------------- Matern kernels
+def _nu2(nu2):
+    if nu2 not in (3, 5):
+        raise ValueError("nu2 (twice the Matern smoothness) must be 3 or 5")
+    return int(nu2)
+
+
+def matern_kuf(X, Z, variance, lengthscales, nu2, out=None):
+    """Matern Kuf = K(Z, X) [M, N] float32 (mgp_matern_kuf)."""
+    _check(X, "X", 2), _check(Z, "Z", 2), _check(variance, "variance"), _check(lengthscales, "lengthscales")
+    N, D = X.shape
+    M = Z.shape[0]
+    if Z.shape[1] != D:
+        raise ValueError("X and Z must have the same number of columns")
+    if out is None:
+        out = padded(M, N, X.device)
+    _lib.call("mgp_matern_kuf", X, _ld(X), Z, _ld(Z), N, M, D, variance, lengthscales, lengthscales.numel(),
+              _nu2(nu2), out, _ld(out), _stream())
+    return out
+
+
+def matern_kuu(Z, variance, lengthscales, nu2, jitter, out=None):
+    """Matern Kuu = K(Z, Z) + jitter I [M, M] float32 (mgp_matern_kuu)."""
+    _check(Z, "Z", 2)
+    M, D = Z.shape
+    if out is None:
+        out = padded(M, M, Z.device)
+    _lib.call("mgp_matern_kuu", Z, _ld(Z), M, D, variance, lengthscales, lengthscales.numel(), _nu2(nu2),
+              float(jitter), out, _ld(out), _stream())
+    return out
+
+
+def matern_kuf_image(X, Z, variance, lengthscales, nu2, out=None, fmt="x6"):
+    """K1 for Matern: the fragment image of Kuf = K(Z, X) (uint8 device tensor), split-bf16
+    (fmt "x6") or split-f16 ("f16"), as rbf_kuf_x6 writes it (mgp_matern_kuf_image)."""
+    _check(X, "X", 2), _check(Z, "Z", 2)
+    N, D = X.shape
+    M = Z.shape[0]
+    out = _workspace("mgp_x6_cols_bytes", (M, N), out, X.device)
+    _lib.call("mgp_matern_kuf_image", X, _ld(X), Z, _ld(Z), N, M, D, variance, lengthscales, lengthscales.numel(),
+              _nu2(nu2), out, out.numel(), {"x6": 0, "f16": 1}[_fmt(fmt)], _stream())
+    return out
+
+
+def matern_kuu_potrf_trtri(Z, variance, lengthscales, nu2, jitter, LinvT=None, L=None, info=None, workspace=None,
+                           want_L=False):
+    """One layer's Matern Kuu (float64, from Z) + Cholesky + inverse (mgp_matern_kuu_potrf_trtri):
+    L (or None), LinvT [1, M, M] and info int32 [1], as kuu_potrf_trtri returns them."""
+    _check(Z, "Z", 2)
+    M, D = Z.shape
+    dev = Z.device
+    if LinvT is None:
+        LinvT = padded(M, M, dev, batch=1)
+    if want_L and L is None:
+        L = padded(M, M, dev, batch=1)
+    if L is not None and _ld(L) != _ld(LinvT):
+        raise ValueError("L and LinvT must share a layout")
+    if info is None:
+        info = torch.empty(1, dtype=torch.int32, device=dev)
+    workspace = _workspace("mgp_matern_chol_workspace_bytes", (M,), workspace, dev)
+    _lib.call("mgp_matern_kuu_potrf_trtri", Z, _ld(Z), M, D, variance, lengthscales, lengthscales.numel(), _nu2(nu2),
+              float(jitter), L, LinvT, _ld(LinvT), info, workspace, workspace.numel(), _stream())
+    return L, LinvT, info
+
+
+def matern_backward(X, Z, variance, lengthscales, nu2, gK, symmetric=False, accumulate=False, gZ=None, g_var=None,
+                    g_ls=None, workspace=None):
+    """Reverse mode of the Matern K(Z, X), as rbf_backward (mgp_matern_backward)."""
+    _check(X, "X", 2), _check(Z, "Z", 2), _check(gK, "gK", 2)
+    N, D = X.shape
+    M = Z.shape[0]
+    dev = X.device
+    n_ls = lengthscales.numel()
+    if gZ is None:
+        gZ = torch.zeros(M, D, dtype=torch.float32, device=dev)
+    if g_var is None:
+        g_var = torch.zeros(1, dtype=torch.float64, device=dev)
+    if g_ls is None:
+        g_ls = torch.zeros(n_ls, dtype=torch.float64, device=dev)
+    workspace = _workspace("mgp_matern_backward_workspace_bytes", (N, M, D), workspace, dev)
+    _lib.call("mgp_matern_backward", X, _ld(X), Z, _ld(Z), N, M, D, variance, lengthscales, n_ls, _nu2(nu2), gK,
+              _ld(gK), int(symmetric), int(accumulate), gZ, _ld(gZ), g_var, g_ls, workspace, workspace.numel(),
+              _stream())
+    return gZ, g_var, g_ls
+
+
 def _same_ld(ts, what):
     if any(_ld(t) != _ld(ts[0]) for t in ts):
         raise ValueError(f"every layer's {what} must share its leading dimension")
