@@ -326,8 +326,6 @@ __global__ __launch_bounds__(kThreads) void result_kernel(
   }
 }
 
-static int padded_d(int D) { return D <= 1 ? 1 : D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : 32; }
-
 static bool in_limits(int64_t N, int D) { return D <= kMaxD && N <= kMaxN; }
 
 }  // namespace greedy
@@ -386,24 +384,17 @@ extern "C" int mgp_greedy_steps(const float* X, int64_t ldx, int64_t N, int32_t 
   State* st = (State*)(ws + lay.state);
   const int64_t nb = B < M ? B : M;   // steps beyond M would return at once
   const dim3 grid((unsigned)lay.NB), block(greedy::kThreads);
-#define MGP_GREEDY_STEP(DPV)                                                                                        \
-  hipLaunchKernelGGL((greedy::step_kernel<DPV>), grid, block, 0, s, X, ldx, N, D, variance, lengthscales, n_ls, M, \
-                     (int)b, L, ldl, (const State*)st, &st->stop_step, (double*)(ws + lay.d),                      \
-                     (double*)(ws + lay.pmax), (double*)(ws + lay.psum), (int64_t*)(ws + lay.pidx),                \
-                     (int64_t*)(ws + lay.piv), (double*)(ws + lay.dmax), (double*)(ws + lay.trace))
   for (int64_t b = 0; b < nb; ++b) {
-    switch (greedy::padded_d(D)) {
-      case 1: MGP_GREEDY_STEP(1); break;
-      case 2: MGP_GREEDY_STEP(2); break;
-      case 4: MGP_GREEDY_STEP(4); break;
-      case 8: MGP_GREEDY_STEP(8); break;
-      case 16: MGP_GREEDY_STEP(16); break;
-      default: MGP_GREEDY_STEP(32); break;
-    }
-    const int rc = launch_status();
+    const int rc = dispatch_dmax(D, [&](auto dm) {
+      hipLaunchKernelGGL((greedy::step_kernel<decltype(dm)::value>), grid, block, 0, s, X, ldx, N, D, variance,
+                         lengthscales, n_ls, M, (int)b, L, ldl, (const State*)st, &st->stop_step,
+                         (double*)(ws + lay.d), (double*)(ws + lay.pmax), (double*)(ws + lay.psum),
+                         (int64_t*)(ws + lay.pidx), (int64_t*)(ws + lay.piv), (double*)(ws + lay.dmax),
+                         (double*)(ws + lay.trace));
+      return launch_status();
+    });
     if (rc) return rc;
   }
-#undef MGP_GREEDY_STEP
   hipLaunchKernelGGL(greedy::commit_kernel, dim3(1), dim3(64), 0, s, st, M, (int)nb, state);
   return launch_status();
 }

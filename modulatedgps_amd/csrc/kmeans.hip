@@ -405,51 +405,34 @@ __global__ __launch_bounds__(kThreads) void select_kernel(const RunState* __rest
   for (int64_t e = threadIdx.x; e < ne; e += kThreads) out[(e / D) * ldcb + e % D] = cb[(int64_t)w * k * D + e];
 }
 
-static int padded_d(int D) { return D <= 1 ? 1 : D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : 32; }
-
 // st, partials, cnt == nullptr: a plain vq (no run state, no block partials, no member counts)
 static int launch_assign(const float* obs, int64_t ldo, int64_t N, int D, const float* cb, int64_t ldc,
                          int64_t cb_stride, int64_t k, int R, const RunState* st, int32_t* code, float* dist,
                          double* partials, int64_t p_stride, int32_t* cnt, int64_t cnt_stride, hipStream_t s) {
   const int lanes = lanes_for(N);
   const dim3 grid((unsigned)assign_blocks(N), (unsigned)R);
-#define MGP_KM_ASSIGN(DPV, LV)                                                                                   \
+#define MGP_KM_ASSIGN(LV)                                                                                       \
   hipLaunchKernelGGL((assign_kernel<DPV, LV>), grid, dim3(kThreads), 0, s, obs, ldo, N, D, cb, ldc, cb_stride, k, \
                      st, code, dist, N, partials, p_stride, cnt, cnt_stride)
-#define MGP_KM_LANES(DPV)                                  \
-  if (lanes == 1) MGP_KM_ASSIGN(DPV, 1);                   \
-  else if (lanes == 4) MGP_KM_ASSIGN(DPV, 4);              \
-  else MGP_KM_ASSIGN(DPV, 16)
-  switch (padded_d(D)) {
-    case 1: MGP_KM_LANES(1); break;
-    case 2: MGP_KM_LANES(2); break;
-    case 4: MGP_KM_LANES(4); break;
-    case 8: MGP_KM_LANES(8); break;
-    case 16: MGP_KM_LANES(16); break;
-    default: MGP_KM_LANES(32); break;
-  }
-#undef MGP_KM_LANES
+  return dispatch_dmax(D, [&](auto dm) {
+    constexpr int DPV = decltype(dm)::value;
+    if (lanes == 1) MGP_KM_ASSIGN(1);
+    else if (lanes == 4) MGP_KM_ASSIGN(4);
+    else MGP_KM_ASSIGN(16);
+    return launch_status();
+  });
 #undef MGP_KM_ASSIGN
-  return launch_status();
 }
 
 static int launch_segsum(const float* obs, int64_t ldo, int64_t N, int D, const RunState* st, int64_t k, int R,
                          const int32_t* sorted, const int32_t* counts, const int32_t* segoff, float* out,
                          int64_t ldout, int64_t out_stride, hipStream_t s) {
   const dim3 grid((unsigned)((k + kThreads / 64 - 1) / (kThreads / 64)), (unsigned)R);
-#define MGP_KM_SEG(DPV)                                                                                         \
-  hipLaunchKernelGGL((segsum_kernel<DPV>), grid, dim3(kThreads), 0, s, obs, ldo, N, D, st, k, sorted, N, counts, \
-                     segoff, k, out, ldout, out_stride)
-  switch (padded_d(D)) {
-    case 1: MGP_KM_SEG(1); break;
-    case 2: MGP_KM_SEG(2); break;
-    case 4: MGP_KM_SEG(4); break;
-    case 8: MGP_KM_SEG(8); break;
-    case 16: MGP_KM_SEG(16); break;
-    default: MGP_KM_SEG(32); break;
-  }
-#undef MGP_KM_SEG
-  return launch_status();
+  return dispatch_dmax(D, [&](auto dm) {
+    hipLaunchKernelGGL((segsum_kernel<decltype(dm)::value>), grid, dim3(kThreads), 0, s, obs, ldo, N, D, st, k,
+                       sorted, N, counts, segoff, k, out, ldout, out_stride);
+    return launch_status();
+  });
 }
 
 // the update half of an iteration: cnt (zeroed, then counted) -> counts, segoff, sorted -> means

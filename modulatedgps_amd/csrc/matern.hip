@@ -1,7 +1,9 @@
 // Matern-3/2 and Matern-5/2 covariance blocks beside rbf.hip's SquaredExponential ones:
 // Kuf = K(Z, X) and Kuu = K(Z, Z) + jitter I in float32, K1 for Matern (the Kuf fragment
 // image of frag_image.hpp, written directly), Kuu in float64 for K3's float64-input path,
-// and the reverse mode of K(Z, X).
+// and the reverse mode of K(Z, X).  The float32 tile kernel and the backward's rows, fold
+// and finish are stationary.hpp's templates, instantiated here for FamMatern; this file
+// holds the family, K1, the float64 Kuu and the entries.
 //
 // Reference: GPflow 2.7 Matern32 / Matern52 (IsotropicStationary.K_r) as the original
 // ModulatedGPs used them in place of SquaredExponential at MixtureGPs/models.py:135, 139.
@@ -21,80 +23,53 @@
 // plus ~10 for sqrt / exp / polynomial, against 4 B (f32), 6 B (image) written per element.
 #include "kuf_image.hpp"
 #include "mgp_common.hpp"
+#include "stationary.hpp"
 
 namespace mgp {
 
 constexpr int kMatThreads = 256;
-constexpr int kMatCols = 4;                        // columns per thread (f32 kernel)
-constexpr int kMatTileN = kMatThreads * kMatCols;  // 1024 columns per workgroup
-constexpr int kMatTileM = 64;                      // rows per workgroup
 
-__host__ __device__ inline float matern_sqrt_nu(int nu2) { return nu2 == 5 ? 2.2360679774997897f : 1.7320508075688772f; }
-__host__ __device__ inline float matern_q3(int nu2) { return nu2 == 5 ? (1.f / 3.f) : 0.f; }
-
-// k / var from s^2 (v_sqrt_f32, v_exp_f32)
-__device__ __forceinline__ float matern_unit(float s2, float q3) {
-  const float s = __builtin_amdgcn_sqrtf(s2);
-  return fmaf(s, fmaf(s, q3, 1.f), 1.f) * __expf(-s);
-}
-
-// ------------------------------------------------------------------ float32 Kuf / Kuu
-// Layout as rbf.hip's rbf_kernel: out [M][ldo], a thread owns 4 consecutive columns (one
-// float4 store per row), the tile's raw Z rows staged in LDS and read as broadcasts.
-template <int DMAX>
-__global__ __launch_bounds__(kMatThreads) void matern_kernel(
-    const float* __restrict__ X, int64_t ldx, const float* __restrict__ Z, int64_t ldz, int64_t N, int64_t M, int D,
-    const float* __restrict__ variance, const float* __restrict__ ls, int n_ls, int nu2, float jitter,
-    float* __restrict__ out, int64_t ldo) {
-  __shared__ float zs[kMatTileM][DMAX];
-  __shared__ float cs[DMAX];
-  const int t = threadIdx.x;
-  const int64_t n0 = (int64_t)blockIdx.x * kMatTileN + (int64_t)t * kMatCols;
-  const int64_t m0 = (int64_t)blockIdx.y * kMatTileM;
-  if (t < DMAX) cs[t] = (t < D) ? matern_sqrt_nu(nu2) / ls[n_ls == 1 ? 0 : t] : 0.f;
-  for (int i = t; i < kMatTileM * DMAX; i += kMatThreads) {
-    const int r = i / DMAX, d = i % DMAX;
-    const int64_t m = m0 + r;
-    zs[r][d] = (m < M && d < D) ? Z[m * ldz + d] : 0.f;
+// Matern-3/2 and 5/2 as one family of stationary.hpp; nu2 is run-time data, so one
+// instruction stream serves both.  Tile and backward: c_d = sqrt(nu2) / l_d on the raw
+// difference.  Backward: with g(s) = dk / d(r^2) / var (nu2 = 3: -(3/2) e^-s; nu2 = 5:
+// -(5/6)(1 + s) e^-s; nothing divides by s) and w = gK var g the sums are
+//   S0_m = sum_n gK k / var,  T1_md = sum_n w (z_d - x_d),  T2_md = sum_n w (z_d - x_d)^2:
+//   g_var = sum_m S0,  gZ_md = 2 T1_md / l_d^2,  g_ls_d = -2 sum_m T2_md / l_d^3.
+struct FamMatern {
+  int nu2;
+  static constexpr bool kStageScaled = false;
+  static constexpr double kGz = 2.0, kGl = -2.0;
+  static constexpr bool kS0OverVar = false;
+  __device__ float q3() const { return nu2 == 5 ? (1.f / 3.f) : 0.f; }
+  __device__ float tile_coef(float l) const { return (nu2 == 5 ? 2.2360679774997897f : 1.7320508075688772f) / l; }
+  __device__ float bwd_coef(float l) const { return tile_coef(l); }
+  // k / var from s^2 (v_sqrt_f32, v_exp_f32)
+  __device__ float unit(float s2) const {
+    const float s = __builtin_amdgcn_sqrtf(s2);
+    return fmaf(s, fmaf(s, q3(), 1.f), 1.f) * __expf(-s);
   }
-  float xs[kMatCols][DMAX];
+  template <int DMAX>
+  __device__ void bwd_point(const float (&c)[DMAX], float var, const float (&x)[DMAX], const float (&z)[DMAX],
+                            float g, float (&acc)[1 + 2 * DMAX]) const {
+    const float ga = nu2 == 5 ? -(5.f / 6.f) : -1.5f, gb = nu2 == 5 ? 1.f : 0.f;
+    float dx[DMAX], s2 = 0.f;
 #pragma unroll
-  for (int j = 0; j < kMatCols; ++j) {
-    const int64_t n = n0 + j;
-#pragma unroll
-    for (int d = 0; d < DMAX; ++d) xs[j][d] = (n < N && d < D) ? X[n * ldx + d] : 0.f;
-  }
-  const float var = variance[0], q3 = matern_q3(nu2);
-  __syncthreads();
-  float c[DMAX];
-#pragma unroll
-  for (int d = 0; d < DMAX; ++d) c[d] = cs[d];
-
-  const int rows = (int)((M - m0) < kMatTileM ? (M - m0) : kMatTileM);
-  for (int r = 0; r < rows; ++r) {
-    const int64_t m = m0 + r;
-    float v[kMatCols];
-#pragma unroll
-    for (int j = 0; j < kMatCols; ++j) {
-      float acc = 0.f;
-#pragma unroll
-      for (int d = 0; d < DMAX; ++d) {
-        const float tt = (zs[r][d] - xs[j][d]) * c[d];
-        acc = fmaf(tt, tt, acc);
-      }
-      v[j] = var * matern_unit(acc, q3);
-      if (jitter != 0.f && m == n0 + j) v[j] += jitter;
+    for (int d = 0; d < DMAX; ++d) {
+      dx[d] = z[d] - x[d];
+      const float tt = dx[d] * c[d];
+      s2 = fmaf(tt, tt, s2);
     }
-    float* o = out + m * ldo + n0;
-    if (n0 + kMatCols <= N) {
-      *reinterpret_cast<floatx4*>(o) = floatx4{v[0], v[1], v[2], v[3]};
-    } else {
+    const float s = __builtin_amdgcn_sqrtf(s2), e = __expf(-s);
+    acc[0] = fmaf(g, fmaf(s, fmaf(s, q3(), 1.f), 1.f) * e, acc[0]);
+    const float wv = g * (var * (ga * fmaf(s, gb, 1.f) * e));
 #pragma unroll
-      for (int j = 0; j < kMatCols; ++j)
-        if (n0 + j < N) o[j] = v[j];
+    for (int d = 0; d < DMAX; ++d) {
+      const float tw = wv * dx[d];
+      acc[1 + d] += tw;
+      acc[1 + DMAX + d] = fmaf(tw, dx[d], acc[1 + DMAX + d]);
     }
   }
-}
+};
 
 // ------------------------------------------------------------------ K1 for Matern
 // The Kuf fragment image (frag_image.hpp: Afr[nb][mk][plane][lane][8]) without an f32 Kuf.
@@ -110,6 +85,7 @@ __global__ __launch_bounds__(kMatThreads) void matern_kuf_image_kernel(
     const float* __restrict__ X, int64_t ldx, const float* __restrict__ Z, int64_t ldz, int64_t N, int64_t M, int D,
     const float* __restrict__ variance, const float* __restrict__ ls, int n_ls, int nu2, int nmk, int row_blocks,
     bf16x8* __restrict__ Kfr, float* __restrict__ tr) {
+  const FamMatern fam{nu2};
   __shared__ float zs[kKufRows][DMAX];
   __shared__ float cs[DMAX];
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, h = lane >> 5, c32 = lane & 31;
@@ -118,7 +94,7 @@ __global__ __launch_bounds__(kMatThreads) void matern_kuf_image_kernel(
   const int64_t nb = cg * 4 + w;
   const int64_t n = 32 * nb + c32;
   const int64_t m0 = kKufRows * rb;
-  if (t < DMAX) cs[t] = (t < D) ? matern_sqrt_nu(nu2) / ls[n_ls == 1 ? 0 : t] : 0.f;
+  if (t < DMAX) cs[t] = (t < D) ? fam.tile_coef(ls[n_ls == 1 ? 0 : t]) : 0.f;
   for (int i = t; i < kKufRows * DMAX; i += kMatThreads) {
     const int r = i / DMAX, d = i % DMAX;
     const int64_t m = m0 + r;
@@ -127,7 +103,7 @@ __global__ __launch_bounds__(kMatThreads) void matern_kuf_image_kernel(
   float x[DMAX];
 #pragma unroll
   for (int d = 0; d < DMAX; ++d) x[d] = (n < N && d < D) ? X[n * ldx + d] : 0.f;
-  const float var = variance[0], q3 = matern_q3(nu2);
+  const float var = variance[0];
   if (bid == 0) {
     if (t == 0) tr[0] = var;
     if (t >= kKufCentreFloats && t < 2 * kKufCentreFloats) tr[t] = 0.f;
@@ -151,7 +127,7 @@ __global__ __launch_bounds__(kMatThreads) void matern_kuf_image_kernel(
         const float tt = (zs[r][d] - x[d]) * c[d];
         acc = fmaf(tt, tt, acc);
       }
-      v[j] = matern_unit(acc, q3) * mult;
+      v[j] = fam.unit(acc) * mult;
       if (!col_ok || m0 + r >= M) v[j] = 0.f;
       // the split must see v as the rounded f32 product (kuf_image.hpp: without this the
       // multiply is contracted into the hi / lo conversions and the planes disagree)
@@ -183,168 +159,6 @@ __global__ __launch_bounds__(256) void matern_kuu_f64_kernel(const float* __rest
   out[i * ld + j] = (double)variance[0] * p * exp(-s) + (i == j ? jitter : 0.0);
 }
 
-// ------------------------------------------------------------------ backward
-// Reverse mode of K(Z, X) for a cotangent gK [M][N].  With g(s) = dk / d(r^2) / var
-// (nu2 = 3: -(3/2) e^-s; nu2 = 5: -(5/6)(1 + s) e^-s; nothing divides by s), w = gK var g and
-//   S0_m = sum_n gK k / var,  T1_md = sum_n w (z_d - x_d),  T2_md = sum_n w (z_d - x_d)^2:
-//   g_var = sum_m S0,  gZ_md = 2 T1_md / l_d^2,  g_ls_d = -2 sum_m T2_md / l_d^3.
-// Coincident points contribute exact zeros to T1 and T2.  For Kuu (X = Z, symmetric gK) z
-// enters both arguments: gZ doubles.  Kernel 1 as rbf.hip's: 4 waves x 2 rows of Z per
-// block, lanes stride over an n-chunk (VEC: ldx % 4 == 0, ldx >= DMAX and X 16-byte aligned, a
-// point's coordinates come in DMAX / 4 dwordx4 loads); each lane accumulates its <= 64 points in float32,
-// the lane reduction and everything after it is float64 in a fixed order (kernel 2 folds
-// the chunks, kernel 3 writes the gradients; no atomics: two calls give the same bits).
-constexpr int kMatRows = 2;       // rows of Z per wave
-constexpr int64_t kMatChunk = 4096;
-
-template <int DMAX, bool VEC>
-__global__ __launch_bounds__(256) void matern_bwd_rows_kernel(
-    const float* __restrict__ X, int64_t ldx, const float* __restrict__ Z, int64_t ldz, int64_t N, int64_t M, int D,
-    const float* __restrict__ variance, const float* __restrict__ ls, int n_ls, int nu2,
-    const float* __restrict__ gK, int64_t ldg, double* __restrict__ part_all) {
-  constexpr int NS = 1 + 2 * DMAX, R = kMatRows;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t m0 = (int64_t)blockIdx.x * 4 * R + R * w;
-  const int64_t nb = (int64_t)blockIdx.y * kMatChunk;
-  const int64_t ne = (nb + kMatChunk < N) ? nb + kMatChunk : N;
-  double* part = part_all + (int64_t)blockIdx.y * M * NS;
-  float c[DMAX], z[R][DMAX];
-#pragma unroll
-  for (int d = 0; d < DMAX; ++d) c[d] = (d < D) ? matern_sqrt_nu(nu2) / ls[n_ls == 1 ? 0 : d] : 0.f;
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int d = 0; d < DMAX; ++d) z[r][d] = (m0 + r < M && d < D) ? Z[(m0 + r) * ldz + d] : 0.f;
-  const float var = variance[0], q3 = matern_q3(nu2);
-  const float ga = nu2 == 5 ? -(5.f / 6.f) : -1.5f, gb = nu2 == 5 ? 1.f : 0.f;
-  float acc[R][NS];
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int j = 0; j < NS; ++j) acc[r][j] = 0.f;
-  auto point = [&](int64_t n) {
-    float x[DMAX], g[R];
-    if constexpr (VEC) {
-#pragma unroll
-      for (int q4 = 0; q4 < DMAX / 4; ++q4) {
-        const floatx4 v = *reinterpret_cast<const floatx4*>(X + n * ldx + 4 * q4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) x[4 * q4 + j] = (4 * q4 + j < D) ? v[j] : 0.f;
-      }
-    } else {
-#pragma unroll
-      for (int d = 0; d < DMAX; ++d) x[d] = (d < D) ? X[n * ldx + d] : 0.f;
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) g[r] = (m0 + r < M) ? gK[(m0 + r) * ldg + n] : 0.f;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      float dx[DMAX], s2 = 0.f;
-#pragma unroll
-      for (int d = 0; d < DMAX; ++d) {
-        dx[d] = z[r][d] - x[d];
-        const float tt = dx[d] * c[d];
-        s2 = fmaf(tt, tt, s2);
-      }
-      const float s = __builtin_amdgcn_sqrtf(s2), e = __expf(-s);
-      acc[r][0] = fmaf(g[r], fmaf(s, fmaf(s, q3, 1.f), 1.f) * e, acc[r][0]);
-      const float wv = g[r] * (var * (ga * fmaf(s, gb, 1.f) * e));
-#pragma unroll
-      for (int d = 0; d < DMAX; ++d) {
-        const float tw = wv * dx[d];
-        acc[r][1 + d] += tw;
-        acc[r][1 + DMAX + d] = fmaf(tw, dx[d], acc[r][1 + DMAX + d]);
-      }
-    }
-  };
-  int64_t n = nb + lane;
-  for (; n + 192 < ne; n += 256) {   // four points' loads in flight
-    point(n);
-    point(n + 64);
-    point(n + 128);
-    point(n + 192);
-  }
-  for (; n < ne; n += 64) point(n);
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int j = 0; j < NS; ++j) {
-      const double v = wave_sum<double>((double)acc[r][j]);
-      if (lane == 0 && m0 + r < M) part[(m0 + r) * NS + j] = v;
-    }
-}
-
-// part[0][idx] = sum over the chunks of part[ch][idx], one thread per idx, fixed order
-__global__ __launch_bounds__(256) void matern_bwd_fold_kernel(double* __restrict__ part, int nchunks, int64_t total) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  double v = part[idx];
-  for (int ch = 1; ch < nchunks; ++ch) v += part[(int64_t)ch * total + idx];
-  part[idx] = v;
-}
-
-template <int DMAX>
-__global__ __launch_bounds__(256) void matern_bwd_finish_kernel(const double* __restrict__ part, int64_t M, int D,
-                                                                const float* __restrict__ ls, int n_ls, float zfactor,
-                                                                int accumulate, float* __restrict__ gZ, int64_t ldgz,
-                                                                double* __restrict__ g_var, double* __restrict__ g_ls) {
-  constexpr int NS = 1 + 2 * DMAX;
-  __shared__ double scratch[16];
-  double gl[DMAX], il[DMAX], s0tot = 0.0;
-#pragma unroll
-  for (int d = 0; d < DMAX; ++d) {
-    gl[d] = 0.0;
-    il[d] = (d < D) ? 1.0 / (double)ls[n_ls == 1 ? 0 : d] : 0.0;
-  }
-  for (int64_t m = threadIdx.x; m < M; m += 256) {
-    s0tot += part[m * NS];
-#pragma unroll
-    for (int d = 0; d < DMAX; ++d) {
-      if (d >= D) break;
-      const double gz = (double)zfactor * 2.0 * il[d] * il[d] * part[m * NS + 1 + d];
-      gZ[m * ldgz + d] = (float)(accumulate ? (double)gZ[m * ldgz + d] + gz : gz);
-      gl[d] += -2.0 * il[d] * il[d] * il[d] * part[m * NS + 1 + DMAX + d];
-    }
-  }
-  const double gv = block_sum<double>(s0tot, scratch);
-  if (threadIdx.x == 0) *g_var = accumulate ? *g_var + gv : gv;
-  double giso = 0.0;
-#pragma unroll
-  for (int d = 0; d < DMAX; ++d) {
-    if (d >= D) break;
-    __syncthreads();
-    const double v = block_sum<double>(gl[d], scratch);
-    if (threadIdx.x == 0) {
-      if (n_ls == 1) giso += v;
-      else g_ls[d] = accumulate ? g_ls[d] + v : v;
-    }
-  }
-  if (threadIdx.x == 0 && n_ls == 1) g_ls[0] = accumulate ? g_ls[0] + giso : giso;
-}
-
-static int matern_dmax(int D) { return D <= 1 ? 1 : D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : 32; }
-
-static int matern_launch(const float* X, int64_t ldx, const float* Z, int64_t ldz, int64_t N, int64_t M, int D,
-                         const float* variance, const float* ls, int n_ls, int nu2, float jitter, float* out,
-                         int64_t ldo, hipStream_t stream) {
-  dim3 grid((unsigned)((N + kMatTileN - 1) / kMatTileN), (unsigned)((M + kMatTileM - 1) / kMatTileM));
-  dim3 block(kMatThreads);
-#define MGP_MAT_CASE(DM)                                                                                  \
-  if (D <= DM) {                                                                                          \
-    hipLaunchKernelGGL(matern_kernel<DM>, grid, block, 0, stream, X, ldx, Z, ldz, N, M, D, variance, ls,   \
-                       n_ls, nu2, jitter, out, ldo);                                                      \
-    return launch_status();                                                                               \
-  }
-  MGP_MAT_CASE(1)
-  MGP_MAT_CASE(2)
-  MGP_MAT_CASE(4)
-  MGP_MAT_CASE(8)
-  MGP_MAT_CASE(16)
-  MGP_MAT_CASE(32)
-#undef MGP_MAT_CASE
-  return MGP_ERR_UNSUPPORTED;
-}
-
 }  // namespace mgp
 
 using namespace mgp;
@@ -366,8 +180,8 @@ extern "C" int mgp_matern_kuf(const float* X, int64_t ldx, const float* Z, int64
   if (ldk < N) return -13;
   if (ldk % 4 || !aligned16(Kuf)) return MGP_ERR_ALIGN;
   if (N <= 0 || M <= 0) return MGP_OK;
-  return matern_launch(X, ldx, Z, ldz, N, M, D, variance, lengthscales, n_ls, nu2, 0.f, Kuf, ldk,
-                       (hipStream_t)stream);
+  return stat_tile_launch(FamMatern{nu2}, X, ldx, Z, ldz, N, M, D, variance, lengthscales, n_ls, 0.f, Kuf, ldk,
+                          (hipStream_t)stream);
 }
 
 extern "C" int mgp_matern_kuu(const float* Z, int64_t ldz, int64_t M, int32_t D, const float* variance,
@@ -386,8 +200,8 @@ extern "C" int mgp_matern_kuu(const float* Z, int64_t ldz, int64_t M, int32_t D,
   if (ldk < M) return -11;
   if (ldk % 4 || !aligned16(Kuu)) return MGP_ERR_ALIGN;
   if (M <= 0) return MGP_OK;
-  return matern_launch(Z, ldz, Z, ldz, M, M, D, variance, lengthscales, n_ls, nu2, jitter, Kuu, ldk,
-                       (hipStream_t)stream);
+  return stat_tile_launch(FamMatern{nu2}, Z, ldz, Z, ldz, M, M, D, variance, lengthscales, n_ls, jitter, Kuu, ldk,
+                          (hipStream_t)stream);
 }
 
 extern "C" int mgp_matern_kuf_image(const float* X, int64_t ldx, const float* Z, int64_t ldz, int64_t N, int64_t M,
@@ -413,24 +227,16 @@ extern "C" int mgp_matern_kuf_image(const float* X, int64_t ldx, const float* Z,
   const dim3 grid((unsigned)kuf_blocks(M, N)), block(kMatThreads);
   hipStream_t s = (hipStream_t)stream;
   float* tr = trailer(Kfr, cols_planes(M, N));
-#define MGP_MAT_IMG_CASE(DM)                                                                                 \
-  if (D <= DM) {                                                                                             \
-    if (kfr_format == 1)                                                                                     \
-      hipLaunchKernelGGL((matern_kuf_image_kernel<DM, true>), grid, block, 0, s, X, ldx, Z, ldz, N, M, D,     \
-                         variance, lengthscales, n_ls, nu2, nmk, row_blocks, (bf16x8*)Kfr, tr);              \
-    else                                                                                                     \
-      hipLaunchKernelGGL((matern_kuf_image_kernel<DM, false>), grid, block, 0, s, X, ldx, Z, ldz, N, M, D,    \
-                         variance, lengthscales, n_ls, nu2, nmk, row_blocks, (bf16x8*)Kfr, tr);              \
-    return launch_status();                                                                                  \
-  }
-  MGP_MAT_IMG_CASE(1)
-  MGP_MAT_IMG_CASE(2)
-  MGP_MAT_IMG_CASE(4)
-  MGP_MAT_IMG_CASE(8)
-  MGP_MAT_IMG_CASE(16)
-  MGP_MAT_IMG_CASE(32)
-#undef MGP_MAT_IMG_CASE
-  return MGP_ERR_UNSUPPORTED;
+  return dispatch_dmax(D, [&](auto dm) {
+    constexpr int DM = decltype(dm)::value;
+    if (kfr_format == 1)
+      hipLaunchKernelGGL((matern_kuf_image_kernel<DM, true>), grid, block, 0, s, X, ldx, Z, ldz, N, M, D, variance,
+                         lengthscales, n_ls, nu2, nmk, row_blocks, (bf16x8*)Kfr, tr);
+    else
+      hipLaunchKernelGGL((matern_kuf_image_kernel<DM, false>), grid, block, 0, s, X, ldx, Z, ldz, N, M, D, variance,
+                         lengthscales, n_ls, nu2, nmk, row_blocks, (bf16x8*)Kfr, tr);
+    return launch_status();
+  });
 }
 
 // K3's workspace for one matrix, then the float64 Kuu [M][M]
@@ -471,8 +277,8 @@ extern "C" int mgp_matern_kuu_potrf_trtri(const float* Z, int64_t ldz, int64_t M
 
 extern "C" size_t mgp_matern_backward_workspace_bytes(int64_t N, int64_t M, int32_t D) {
   if (N < 0 || M <= 0 || D < 1 || D > 32) return 0;
-  const int64_t nch = (N + kMatChunk - 1) / kMatChunk;
-  return (size_t)((nch > 0 ? nch : 1) * M * (1 + 2 * matern_dmax(D))) * sizeof(double);
+  const int64_t nch = stat_bwd_chunks(N);
+  return (size_t)((nch > 0 ? nch : 1) * M * (1 + 2 * dmax_of(D))) * sizeof(double);
 }
 
 extern "C" int mgp_matern_backward(const float* X, int64_t ldx, const float* Z, int64_t ldz, int64_t N, int64_t M,
@@ -498,34 +304,6 @@ extern "C" int mgp_matern_backward(const float* X, int64_t ldx, const float* Z, 
   if (!g_ls) return -19;
   if (N <= 0 || M <= 0) return MGP_OK;
   if (!workspace || workspace_bytes < mgp_matern_backward_workspace_bytes(N, M, D)) return MGP_ERR_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  const int nch = (int)((N + kMatChunk - 1) / kMatChunk);
-  double* part = (double*)workspace;
-  const float zf = symmetric ? 2.f : 1.f;
-  const int acc = accumulate ? 1 : 0;
-  const dim3 grid((unsigned)((M + 4 * kMatRows - 1) / (4 * kMatRows)), (unsigned)nch);
-#define MGP_MAT_BWD_CASE(DM)                                                                                    \
-  if (D <= DM) {                                                                                                \
-    /* the point loads' form only (dwordx4 or dword): the same values either way */                             \
-    if (DM >= 4 && ldx % 4 == 0 && ldx >= DM && aligned16(X))                                                   \
-      hipLaunchKernelGGL((matern_bwd_rows_kernel<DM, (DM >= 4)>), grid, dim3(256), 0, s, X, ldx, Z, ldz, N, M, D, \
-                         variance, lengthscales, n_ls, nu2, gK, ldg, part);                                     \
-    else                                                                                                        \
-      hipLaunchKernelGGL((matern_bwd_rows_kernel<DM, false>), grid, dim3(256), 0, s, X, ldx, Z, ldz, N, M, D,    \
-                         variance, lengthscales, n_ls, nu2, gK, ldg, part);                                     \
-    if (nch > 1)                                                                                                \
-      hipLaunchKernelGGL(matern_bwd_fold_kernel, dim3((unsigned)((M * (1 + 2 * DM) + 255) / 256)), dim3(256), 0, \
-                         s, part, nch, M * (1 + 2 * DM));                                                       \
-    hipLaunchKernelGGL(matern_bwd_finish_kernel<DM>, dim3(1), dim3(256), 0, s, part, M, D, lengthscales, n_ls,   \
-                       zf, acc, gZ, ldgz, g_var, g_ls);                                                         \
-    return launch_status();                                                                                     \
-  }
-  MGP_MAT_BWD_CASE(1)
-  MGP_MAT_BWD_CASE(2)
-  MGP_MAT_BWD_CASE(4)
-  MGP_MAT_BWD_CASE(8)
-  MGP_MAT_BWD_CASE(16)
-  MGP_MAT_BWD_CASE(32)
-#undef MGP_MAT_BWD_CASE
-  return MGP_ERR_UNSUPPORTED;
+  return stat_bwd_launch(FamMatern{nu2}, X, ldx, Z, ldz, N, M, D, variance, lengthscales, n_ls, gK, ldg, symmetric,
+                         accumulate, gZ, ldgz, g_var, g_ls, (double*)workspace, (hipStream_t)stream);
 }

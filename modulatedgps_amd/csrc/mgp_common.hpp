@@ -21,6 +21,22 @@ inline int hip_status(hipError_t e) { return e == hipSuccess ? MGP_OK : MGP_ERR_
 inline int launch_status() { return hip_status(hipGetLastError()); }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// ------------------------------------------------------------------ D dispatch
+// Kernels templated on DMAX hold a point's D <= DMAX coordinates in registers:
+// dmax_of(D) is the smallest instantiated DMAX, and dispatch_dmax(D, f) returns
+// f(std::integral_constant<int, dmax_of(D)>{}), MGP_ERR_UNSUPPORTED for D > 32.
+inline int dmax_of(int D) { return D <= 1 ? 1 : D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : 32; }
+template <class Fn>
+int dispatch_dmax(int D, Fn&& f) {
+  if (D <= 1) return f(std::integral_constant<int, 1>{});
+  if (D <= 2) return f(std::integral_constant<int, 2>{});
+  if (D <= 4) return f(std::integral_constant<int, 4>{});
+  if (D <= 8) return f(std::integral_constant<int, 8>{});
+  if (D <= 16) return f(std::integral_constant<int, 16>{});
+  if (D <= 32) return f(std::integral_constant<int, 32>{});
+  return MGP_ERR_UNSUPPORTED;
+}
+
 // ------------------------------------------------------------------ stats tiles
 // Rows of one tile of the column statistics stats[t][1 + K][N] (sum A^2, A^T q_mu):
 // mgp_stats_tiles(M) = ceil(M / kTgBM) tiles.  Every producer and reader of a stats slot

@@ -5,12 +5,13 @@
 // (self.kernel.K(Z, Xnew)); GPflow 2.7 SquaredExponential.K_r2(r2) =
 // var * exp(-0.5 r2), r2 = square_distance(X / l, X2 / l).
 //
+// The float32 tile kernel (kuf_image.hpp's "rbf_kernel") and the backward's rows, fold and
+// finish are stationary.hpp's templates, instantiated here for FamSE; this file holds the
+// family, K1 (the image kernel), the batched backward and the entries.
+//
 // Roofline: HBM-write bound.  Algorithmic bytes = 4 * (N*D + M*D + M*N); per
 // output element the kernel does D subtracts + D FMAs + 1 exp2, far below the
-// f32 VALU ridge.  Layout: Kuf [M][ldk] row-major (N contiguous); each thread
-// owns 4 consecutive columns (one float4 store per row), a wave writes 1 KiB
-// contiguous per row.  The scaled Z rows of the tile are staged once in LDS
-// and read as wave-uniform broadcasts.
+// f32 VALU ridge.
 //
 // Numerics: direct-difference form sum_d (z_d - x_d)^2 * c_d^2 (exact symmetric,
 // never negative) instead of GPflow's |a|^2 + |b|^2 - 2ab expansion; the
@@ -20,77 +21,83 @@
 // rounding of a scaled coordinate grows with the data's spread about that point, not
 // with its distance from the origin: K(Z + c, X + c) = K(Z, X), bit for bit whenever
 // the shifted coordinates and their differences are exact in float32.
-#include <type_traits>
-
 #include "kuf_image.hpp"
 #include "mgp_common.hpp"
+#include "stationary.hpp"
 
 namespace mgp {
 
-constexpr int kRbfThreads = 256;
-constexpr int kRbfCols = 4;                       // columns per thread
-constexpr int kRbfTileN = kRbfThreads * kRbfCols; // 1024 columns per workgroup
-constexpr int kRbfTileM = 64;                     // rows per workgroup (X re-read M/64 times)
+#ifndef MGP_RBF_PACKED
+#define MGP_RBF_PACKED 1
+#endif
+typedef float floatx2v __attribute__((ext_vector_type(2)));
 
-template <int DMAX>
-__global__ __launch_bounds__(kRbfThreads) void rbf_kernel(
-    const float* __restrict__ X, int64_t ldx, const float* __restrict__ Z, int64_t ldz, int64_t N,
-    int64_t M, int D, const float* __restrict__ variance, const float* __restrict__ ls, int n_ls,
-    float jitter, float* __restrict__ out, int64_t ldo) {
-  __shared__ float zs[kRbfTileM][DMAX];
-  __shared__ float cs[DMAX];
-  const int t = threadIdx.x;
-  const int64_t n0 = (int64_t)blockIdx.x * kRbfTileN + (int64_t)t * kRbfCols;
-  const int64_t m0 = (int64_t)blockIdx.y * kRbfTileM;
-  const float kHalfLog2e = 0.8493218002880191f;  // sqrt(0.5 * log2(e))
-
-  if (t < DMAX) cs[t] = (t < D) ? kHalfLog2e / ls[n_ls == 1 ? 0 : t] : 0.f;
-  __syncthreads();
-  for (int i = t; i < kRbfTileM * DMAX; i += kRbfThreads) {
-    const int r = i / DMAX, d = i % DMAX;
-    const int64_t m = m0 + r;
-    zs[r][d] = (m < M && d < D) ? (Z[m * ldz + d] - Z[d]) * cs[d] : 0.f;
+// SquaredExponential as a family of stationary.hpp.  Tile: c_d = sqrt(0.5 log2 e) / l_d and
+// k / var = exp2(-acc).  Backward: for K = var exp(-1/2 sum_d (z_d - x_d)^2 / l_d^2) and
+// w_mn = gK_mn k_mn the sums are
+//   S0_m = sum_n w_mn,  T1_md = sum_n w_mn (x_nd - z_md),  T2_md = sum_n w_mn (x_nd - z_md)^2
+//   g_var = sum w / var,  g_z_md = T1_md / l_d^2,  g_l_d = sum_m T2_md / l_d^3.
+struct FamSE {
+  static constexpr bool kStageScaled = true;
+  static constexpr double kGz = 1.0, kGl = 1.0;
+  static constexpr bool kS0OverVar = true;
+  __device__ float tile_coef(float l) const { return 0.8493218002880191f / l; }  // sqrt(0.5 * log2(e))
+  __device__ float unit(float acc) const { return exp2f(-acc); }
+  __device__ float bwd_coef(float l) const {  // -1 / (2 l^2)
+    const float c = 1.f / l;
+    return -0.5f * c * c;
   }
-  float xs[kRbfCols][DMAX];
+  template <int DMAX>
+  __device__ void bwd_point(const float (&hc2)[DMAX], float var, const float (&x)[DMAX], const float (&z)[DMAX],
+                            float g, float (&acc)[1 + 2 * DMAX]) const {
+    if constexpr (MGP_RBF_PACKED && DMAX % 2 == 0) {
+      // coordinate pairs on packed f32 VALU ops (v_pk_add / v_pk_mul / v_pk_fma_f32):
+      // half the instructions of the per-coordinate terms
+      floatx2v dx[DMAX / 2], qv = {0.f, 0.f};
 #pragma unroll
-  for (int j = 0; j < kRbfCols; ++j) {
-    const int64_t n = n0 + j;
+      for (int p = 0; p < DMAX / 2; ++p) {
+        dx[p] = floatx2v{x[2 * p], x[2 * p + 1]} - floatx2v{z[2 * p], z[2 * p + 1]};
+        qv = floatx2v{hc2[2 * p], hc2[2 * p + 1]} * dx[p] * dx[p] + qv;
+      }
+      const float wv = g * (var * __expf(qv[0] + qv[1]));
+      acc[0] += wv;
+      const floatx2v w2 = {wv, wv};
 #pragma unroll
-    for (int d = 0; d < DMAX; ++d) xs[j][d] = (n < N && d < D) ? (X[n * ldx + d] - Z[d]) * cs[d] : 0.f;
-  }
-  const float var = variance[0];
-  __syncthreads();
-
-  const int rows = (int)((M - m0) < kRbfTileM ? (M - m0) : kRbfTileM);
-  for (int r = 0; r < rows; ++r) {
-    const int64_t m = m0 + r;
-    float v[kRbfCols];
-#pragma unroll
-    for (int j = 0; j < kRbfCols; ++j) {
-      float acc = 0.f;
+      for (int p = 0; p < DMAX / 2; ++p) {
+        const floatx2v t = w2 * dx[p];
+        floatx2v a1 = {acc[1 + 2 * p], acc[2 + 2 * p]};
+        floatx2v a2 = {acc[1 + DMAX + 2 * p], acc[2 + DMAX + 2 * p]};
+        a1 += t;
+        a2 = t * dx[p] + a2;
+        acc[1 + 2 * p] = a1[0];
+        acc[2 + 2 * p] = a1[1];
+        acc[1 + DMAX + 2 * p] = a2[0];
+        acc[2 + DMAX + 2 * p] = a2[1];
+      }
+    } else {
+      float dx[DMAX], q = 0.f;
 #pragma unroll
       for (int d = 0; d < DMAX; ++d) {
-        const float diff = zs[r][d] - xs[j][d];
-        acc = fmaf(diff, diff, acc);
+        dx[d] = x[d] - z[d];
+        q = fmaf(hc2[d] * dx[d], dx[d], q);
       }
-      v[j] = var * exp2f(-acc);
-      if (jitter != 0.f && m == n0 + j) v[j] += jitter;
-    }
-    float* o = out + m * ldo + n0;
-    if (n0 + kRbfCols <= N) {
-      *reinterpret_cast<floatx4*>(o) = floatx4{v[0], v[1], v[2], v[3]};
-    } else {
+      const float wv = g * (var * __expf(q));
+      acc[0] += wv;
 #pragma unroll
-      for (int j = 0; j < kRbfCols; ++j)
-        if (n0 + j < N) o[j] = v[j];
+      for (int d = 0; d < DMAX; ++d) {
+        const float t = wv * dx[d];
+        acc[1 + d] += t;
+        acc[1 + DMAX + d] = fmaf(t, dx[d], acc[1 + DMAX + d]);
+      }
     }
   }
-}
+};
 
 // K1 writing Kuf's split-bf16 / split-f16 image (frag_image.hpp layout) instead of f32
 // Kuf: one block of kuf_image.hpp per 256-thread workgroup (the body, its layout and
 // numerics are documented there; the K3 step launches run the same blocks as their
 // Kuf side job, mgp_kuu_potrf_trtri_kuf).
+constexpr int kRbfThreads = 256;
 template <int DMAX, bool F16 = false>
 __global__ __launch_bounds__(kRbfThreads) void rbf_kuf_x6_kernel(
     const float* __restrict__ X, int64_t ldx, const float* __restrict__ Z, int64_t ldz, int64_t N,
@@ -100,171 +107,6 @@ __global__ __launch_bounds__(kRbfThreads) void rbf_kuf_x6_kernel(
   const KufImageArgs a = {X, ldx, Z, ldz, N, M, D, variance, ls, n_ls, nmk, row_blocks, Kfr, F16 ? bound : nullptr,
                           bound + kKufCentreFloats};
   kuf_image_block<DMAX, F16>(a, blockIdx.x, threadIdx.x, true, lds);
-}
-
-static int rbf_launch(const float* X, int64_t ldx, const float* Z, int64_t ldz, int64_t N, int64_t M,
-                      int D, const float* variance, const float* ls, int n_ls, float jitter, float* out,
-                      int64_t ldo, hipStream_t stream) {
-  if (N <= 0 || M <= 0) return MGP_OK;
-  dim3 grid((unsigned)((N + kRbfTileN - 1) / kRbfTileN), (unsigned)((M + kRbfTileM - 1) / kRbfTileM));
-  dim3 block(kRbfThreads);
-#define MGP_RBF_CASE(DM)                                                                            \
-  if (D <= DM) {                                                                                     \
-    hipLaunchKernelGGL(rbf_kernel<DM>, grid, block, 0, stream, X, ldx, Z, ldz, N, M, D, variance, ls, \
-                       n_ls, jitter, out, ldo);                                                      \
-    return launch_status();                                                                          \
-  }
-  MGP_RBF_CASE(1)
-  MGP_RBF_CASE(2)
-  MGP_RBF_CASE(4)
-  MGP_RBF_CASE(8)
-  MGP_RBF_CASE(16)
-  MGP_RBF_CASE(32)
-#undef MGP_RBF_CASE
-  return MGP_ERR_UNSUPPORTED;
-}
-
-// ------------------------------------------------------------------ RBF backward
-// Reverse mode of K(Z, X) = var exp(-1/2 sum_d c_d^2 (z_d - x_d)^2), c = 1 / l
-// (models.py:135,139) for a cotangent gK [M][N]: with w_mn = gK_mn k_mn and the
-// centred sums (no cancellation between large terms)
-//   S0_m = sum_n w_mn,  T1_md = sum_n w_mn (x_nd - z_md),  T2_md = sum_n w_mn (x_nd - z_md)^2
-//   g_var = sum w / var,  g_z_md = c_d^2 T1_md,  g_l_d = c_d^3 sum_m T2_md.
-// For Kuu (X = Z, symmetric gK) z enters both arguments: g_z doubles.
-// Kernel 1: 4 waves x 2 rows of Z per block, lanes stride over an n-chunk four
-// points at a time; each lane accumulates its <= 64 points in float32 (sums of
-// centred terms), the lane / chunk reduction is float64.  Kernel 2 folds the
-// chunks (one thread per sum), kernel 3 writes the grads.
-// VEC (ldx % 4 == 0, ldx >= DMAX, X 16-byte aligned): a point's coordinates come
-// in DMAX / 4 dwordx4 loads instead of DMAX dword loads at a 4 ldx-byte lane
-// stride -- the strided dword loads cost the address unit 8x the cycles and
-// bounded this kernel.
-constexpr int kRbfRows = 2;  // rows of Z per wave
-#ifndef MGP_RBF_PACKED
-#define MGP_RBF_PACKED 1
-#endif
-constexpr bool kRbfPacked = MGP_RBF_PACKED;
-typedef float floatx2v __attribute__((ext_vector_type(2)));
-// one workgroup's rows (blockIdx.x) over the points [nb, ne); part: this chunk's [M][NS]
-template <int DMAX, bool VEC>
-__device__ __forceinline__ void rbf_bwd_rows_body(const float* __restrict__ X, int64_t ldx,
-                                                  const float* __restrict__ Z, int64_t ldz, int64_t nb, int64_t ne,
-                                                  int64_t M, int D, const float* __restrict__ variance,
-                                                  const float* __restrict__ ls, int n_ls,
-                                                  const float* __restrict__ gK, int64_t ldg,
-                                                  double* __restrict__ part) {
-  constexpr int NS = 1 + 2 * DMAX, R = kRbfRows;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t m0 = (int64_t)blockIdx.x * 4 * R + R * w;
-  float hc2[DMAX], z[R][DMAX];
-#pragma unroll
-  for (int d = 0; d < DMAX; ++d) {
-    const float c = (d < D) ? 1.f / ls[n_ls == 1 ? 0 : d] : 0.f;
-    hc2[d] = -0.5f * c * c;
-  }
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int d = 0; d < DMAX; ++d) z[r][d] = (m0 + r < M && d < D) ? Z[(m0 + r) * ldz + d] : 0.f;
-  const float var = variance[0];
-  float acc[R][NS];
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int j = 0; j < NS; ++j) acc[r][j] = 0.f;
-  auto point = [&](int64_t n) {
-    float x[DMAX], g[R];
-    if constexpr (VEC && DMAX >= 4) {
-#pragma unroll
-      for (int q4 = 0; q4 < DMAX / 4; ++q4) {
-        const floatx4 v = *reinterpret_cast<const floatx4*>(X + n * ldx + 4 * q4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) x[4 * q4 + j] = (4 * q4 + j < D) ? v[j] : 0.f;
-      }
-    } else {
-#pragma unroll
-      for (int d = 0; d < DMAX; ++d) x[d] = (d < D) ? X[n * ldx + d] : 0.f;
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) g[r] = (m0 + r < M) ? gK[(m0 + r) * ldg + n] : 0.f;
-    if constexpr (kRbfPacked && DMAX % 2 == 0) {
-      // coordinate pairs on packed f32 VALU ops (v_pk_add / v_pk_mul / v_pk_fma_f32):
-      // half the instructions of the per-coordinate terms
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        floatx2v dx[DMAX / 2], qv = {0.f, 0.f};
-#pragma unroll
-        for (int p = 0; p < DMAX / 2; ++p) {
-          dx[p] = floatx2v{x[2 * p], x[2 * p + 1]} - floatx2v{z[r][2 * p], z[r][2 * p + 1]};
-          qv = floatx2v{hc2[2 * p], hc2[2 * p + 1]} * dx[p] * dx[p] + qv;
-        }
-        const float wv = g[r] * (var * __expf(qv[0] + qv[1]));
-        acc[r][0] += wv;
-        const floatx2v w2 = {wv, wv};
-#pragma unroll
-        for (int p = 0; p < DMAX / 2; ++p) {
-          const floatx2v t = w2 * dx[p];
-          floatx2v a1 = {acc[r][1 + 2 * p], acc[r][2 + 2 * p]};
-          floatx2v a2 = {acc[r][1 + DMAX + 2 * p], acc[r][2 + DMAX + 2 * p]};
-          a1 += t;
-          a2 = t * dx[p] + a2;
-          acc[r][1 + 2 * p] = a1[0];
-          acc[r][2 + 2 * p] = a1[1];
-          acc[r][1 + DMAX + 2 * p] = a2[0];
-          acc[r][2 + DMAX + 2 * p] = a2[1];
-        }
-      }
-      return;
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      float dx[DMAX], q = 0.f;
-#pragma unroll
-      for (int d = 0; d < DMAX; ++d) {
-        dx[d] = x[d] - z[r][d];
-        q = fmaf(hc2[d] * dx[d], dx[d], q);
-      }
-      const float wv = g[r] * (var * __expf(q));
-      acc[r][0] += wv;
-#pragma unroll
-      for (int d = 0; d < DMAX; ++d) {
-        const float t = wv * dx[d];
-        acc[r][1 + d] += t;
-        acc[r][1 + DMAX + d] = fmaf(t, dx[d], acc[r][1 + DMAX + d]);
-      }
-    }
-  };
-  int64_t n = nb + lane;
-  for (; n + 192 < ne; n += 256) {
-    point(n);
-    point(n + 64);
-    point(n + 128);
-    point(n + 192);
-  }
-  for (; n < ne; n += 64) point(n);
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int j = 0; j < NS; ++j) {
-      double v = (double)acc[r][j];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-      if (lane == 0 && m0 + r < M) part[(m0 + r) * NS + j] = v;
-    }
-}
-
-template <int DMAX, bool VEC = false>
-__global__ __launch_bounds__(256) void rbf_bwd_rows_kernel(const float* __restrict__ X, int64_t ldx,
-                                                           const float* __restrict__ Z, int64_t ldz, int64_t N,
-                                                           int64_t M, int D, const float* __restrict__ variance,
-                                                           const float* __restrict__ ls, int n_ls,
-                                                           const float* __restrict__ gK, int64_t ldg,
-                                                           int64_t nchunk, double* __restrict__ part) {
-  constexpr int NS = 1 + 2 * DMAX;
-  const int64_t nb = (int64_t)blockIdx.y * nchunk;
-  const int64_t ne = (nb + nchunk < N) ? nb + nchunk : N;
-  rbf_bwd_rows_body<DMAX, VEC>(X, ldx, Z, ldz, nb, ne, M, D, variance, ls, n_ls, gK, ldg,
-                               part + (int64_t)blockIdx.y * M * NS);
 }
 
 // The layers of mgp_rbf_backward_batch: per layer the Kuf cotangent's chunks
@@ -287,82 +129,12 @@ __global__ __launch_bounds__(256) void rbf_bwd_rows_batch_kernel(const float* __
   double* part = ws + (int64_t)b * slab + (int64_t)y * M * NS;
   if (y < nch) {
     const int64_t nb = (int64_t)y * nchunk, ne = (nb + nchunk < N) ? nb + nchunk : N;
-    rbf_bwd_rows_body<DMAX, VEC>(X, ldx, lay.Z[b], ldz, nb, ne, M, D, lay.var[b], lay.ls[b], n_ls, lay.gKuf[b],
-                                 ldgf, part);
+    stat_bwd_rows_body<FamSE, DMAX, VEC>(FamSE{}, X, ldx, lay.Z[b], ldz, nb, ne, M, D, lay.var[b], lay.ls[b], n_ls,
+                                         lay.gKuf[b], ldgf, part);
   } else {
-    rbf_bwd_rows_body<DMAX, VEC>(lay.Z[b], ldz, lay.Z[b], ldz, 0, M, M, D, lay.var[b], lay.ls[b], n_ls,
-                                 lay.gKuu[b], ldgu, part);
+    stat_bwd_rows_body<FamSE, DMAX, VEC>(FamSE{}, lay.Z[b], ldz, lay.Z[b], ldz, 0, M, M, D, lay.var[b], lay.ls[b],
+                                         n_ls, lay.gKuu[b], ldgu, part);
   }
-}
-
-// part[0][m][j] = sum over the chunks of part[ch][m][j] (in place: each thread
-// reads only its own (m, j) of every chunk), one thread per (m, j), fixed order.
-// blockIdx.y: the layer (part advances by slab doubles)
-__global__ __launch_bounds__(256) void rbf_bwd_fold_kernel(double* __restrict__ part, int nchunks, int64_t total,
-                                                           int64_t slab = 0) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  part += blockIdx.y * slab;
-  if (idx >= total) return;
-  double v = part[idx];
-  for (int ch = 1; ch < nchunks; ++ch) v += part[(int64_t)ch * total + idx];
-  part[idx] = v;
-}
-
-template <int DMAX>
-__device__ __forceinline__ void rbf_bwd_finish_body(const double* __restrict__ part, int nchunks, int64_t M, int D,
-                                                    const float* __restrict__ variance, const float* __restrict__ ls,
-                                                    int n_ls, float zfactor, int accumulate, float* __restrict__ gZ,
-                                                    int64_t ldgz, double* __restrict__ g_var,
-                                                    double* __restrict__ g_ls, double* scratch, int acc_var) {
-  constexpr int NS = 1 + 2 * DMAX;
-  double gl[DMAX], s0tot = 0.0;
-#pragma unroll
-  for (int d = 0; d < DMAX; ++d) gl[d] = 0.0;
-  double c[DMAX];
-#pragma unroll
-  for (int d = 0; d < DMAX; ++d) c[d] = (d < D) ? 1.0 / (double)ls[n_ls == 1 ? 0 : d] : 0.0;
-  for (int64_t m = threadIdx.x; m < M; m += 256) {
-    double S[NS];
-#pragma unroll
-    for (int j = 0; j < NS; ++j) S[j] = 0.0;
-    for (int ch = 0; ch < nchunks; ++ch)
-#pragma unroll
-      for (int j = 0; j < NS; ++j) S[j] += part[((int64_t)ch * M + m) * NS + j];
-    s0tot += S[0];
-#pragma unroll
-    for (int d = 0; d < DMAX; ++d) {
-      if (d >= D) break;
-      const double gz = zfactor * c[d] * c[d] * S[1 + d];
-      gZ[m * ldgz + d] = (float)(accumulate ? (double)gZ[m * ldgz + d] + gz : gz);
-      gl[d] += c[d] * c[d] * c[d] * S[1 + DMAX + d];
-    }
-  }
-  const double var = (double)variance[0];
-  const double gv = block_sum<double>(s0tot, scratch) / var;
-  if (threadIdx.x == 0) *g_var = acc_var ? *g_var + gv : gv;
-  double giso = 0.0;
-#pragma unroll
-  for (int d = 0; d < DMAX; ++d) {
-    if (d >= D) break;
-    __syncthreads();
-    const double v = block_sum<double>(gl[d], scratch);
-    if (threadIdx.x == 0) {
-      if (n_ls == 1) giso += v;
-      else g_ls[d] = accumulate ? g_ls[d] + v : v;
-    }
-  }
-  if (threadIdx.x == 0 && n_ls == 1) g_ls[0] = accumulate ? g_ls[0] + giso : giso;
-}
-
-template <int DMAX>
-__global__ __launch_bounds__(256) void rbf_bwd_finish_kernel(const double* __restrict__ part, int nchunks, int64_t M,
-                                                             int D, const float* __restrict__ variance,
-                                                             const float* __restrict__ ls, int n_ls, float zfactor,
-                                                             int accumulate, float* __restrict__ gZ, int64_t ldgz,
-                                                             double* __restrict__ g_var, double* __restrict__ g_ls) {
-  __shared__ double scratch[16];
-  rbf_bwd_finish_body<DMAX>(part, nchunks, M, D, variance, ls, n_ls, zfactor, accumulate, gZ, ldgz, g_var, g_ls,
-                            scratch, accumulate);
 }
 
 // layer blockIdx.x: the Kuf contribution (folded slab 0; accumulate as given), then
@@ -375,11 +147,11 @@ __global__ __launch_bounds__(256) void rbf_bwd_finish_batch_kernel(const double*
   __shared__ double scratch[16];
   const int b = blockIdx.x;
   const double* part = ws + (int64_t)b * slab;
-  rbf_bwd_finish_body<DMAX>(part, 1, M, D, lay.var[b], lay.ls[b], n_ls, 1.f, accumulate & 1, lay.gZ[b], ldgz,
-                            lay.g_var[b], lay.g_ls[b], scratch, accumulate != 0);
+  stat_bwd_finish_body<FamSE, DMAX>(part, M, D, lay.var[b], lay.ls[b], n_ls, 1.f, accumulate & 1, lay.gZ[b], ldgz,
+                                    lay.g_var[b], lay.g_ls[b], scratch, accumulate != 0);
   __syncthreads();
-  rbf_bwd_finish_body<DMAX>(part + (int64_t)nch * M * NS, 1, M, D, lay.var[b], lay.ls[b], n_ls, 2.f, 1, lay.gZ[b],
-                            ldgz, lay.g_var[b], lay.g_ls[b], scratch, 1);
+  stat_bwd_finish_body<FamSE, DMAX>(part + (int64_t)nch * M * NS, M, D, lay.var[b], lay.ls[b], n_ls, 2.f, 1,
+                                    lay.gZ[b], ldgz, lay.g_var[b], lay.g_ls[b], scratch, 1);
 }
 
 }  // namespace mgp
@@ -403,8 +175,8 @@ extern "C" int mgp_rbf_kuf(const float* X, int64_t ldx, const float* Z, int64_t 
   if (!Kuf) return -11;
   if (ldk < N) return -12;
   if (ldk % 4 || !aligned16(Kuf)) return MGP_ERR_ALIGN;
-  return rbf_launch(X, ldx, Z, ldz, N, M, D, variance, lengthscales, n_ls, 0.f, Kuf, ldk,
-                    (hipStream_t)stream);
+  return stat_tile_launch(FamSE{}, X, ldx, Z, ldz, N, M, D, variance, lengthscales, n_ls, 0.f, Kuf, ldk,
+                          (hipStream_t)stream);
 }
 
 extern "C" int mgp_rbf_kuu(const float* Z, int64_t ldz, int64_t M, int32_t D, const float* variance,
@@ -421,8 +193,8 @@ extern "C" int mgp_rbf_kuu(const float* Z, int64_t ldz, int64_t M, int32_t D, co
   if (!Kuu) return -9;
   if (ldk < M) return -10;
   if (ldk % 4 || !aligned16(Kuu)) return MGP_ERR_ALIGN;
-  return rbf_launch(Z, ldz, Z, ldz, M, M, D, variance, lengthscales, n_ls, jitter, Kuu, ldk,
-                    (hipStream_t)stream);
+  return stat_tile_launch(FamSE{}, Z, ldz, Z, ldz, M, M, D, variance, lengthscales, n_ls, jitter, Kuu, ldk,
+                          (hipStream_t)stream);
 }
 
 static int rbf_kuf_image(const float* X, int64_t ldx, const float* Z, int64_t ldz, int64_t N, int64_t M, int32_t D,
@@ -448,24 +220,16 @@ static int rbf_kuf_image(const float* X, int64_t ldx, const float* Z, int64_t ld
   const dim3 grid((unsigned)kuf_blocks(M, N)), block(kRbfThreads);
   hipStream_t s = (hipStream_t)stream;
   float* bound = trailer(Kfr, cols_planes(M, N));  // image trailer (frag_image.hpp)
-#define MGP_RBF_X6_CASE(DM)                                                                            \
-  if (D <= DM) {                                                                                       \
-    if (f16)                                                                                           \
-      hipLaunchKernelGGL((rbf_kuf_x6_kernel<DM, true>), grid, block, 0, s, X, ldx, Z, ldz, N, M, D,    \
-                         variance, lengthscales, n_ls, nmk, (bf16x8*)Kfr, bound, row_blocks);                      \
-    else                                                                                               \
-      hipLaunchKernelGGL((rbf_kuf_x6_kernel<DM, false>), grid, block, 0, s, X, ldx, Z, ldz, N, M, D,   \
-                         variance, lengthscales, n_ls, nmk, (bf16x8*)Kfr, bound, row_blocks);                    \
-    return launch_status();                                                                            \
-  }
-  MGP_RBF_X6_CASE(1)
-  MGP_RBF_X6_CASE(2)
-  MGP_RBF_X6_CASE(4)
-  MGP_RBF_X6_CASE(8)
-  MGP_RBF_X6_CASE(16)
-  MGP_RBF_X6_CASE(32)
-#undef MGP_RBF_X6_CASE
-  return MGP_ERR_UNSUPPORTED;
+  return dispatch_dmax(D, [&](auto dm) {
+    constexpr int DM = decltype(dm)::value;
+    if (f16)
+      hipLaunchKernelGGL((rbf_kuf_x6_kernel<DM, true>), grid, block, 0, s, X, ldx, Z, ldz, N, M, D, variance,
+                         lengthscales, n_ls, nmk, (bf16x8*)Kfr, bound, row_blocks);
+    else
+      hipLaunchKernelGGL((rbf_kuf_x6_kernel<DM, false>), grid, block, 0, s, X, ldx, Z, ldz, N, M, D, variance,
+                         lengthscales, n_ls, nmk, (bf16x8*)Kfr, bound, row_blocks);
+    return launch_status();
+  });
 }
 
 extern "C" int mgp_rbf_kuf_x6(const float* X, int64_t ldx, const float* Z, int64_t ldz, int64_t N, int64_t M,
@@ -480,12 +244,9 @@ extern "C" int mgp_rbf_kuf_f16(const float* X, int64_t ldx, const float* Z, int6
   return rbf_kuf_image(X, ldx, Z, ldz, N, M, D, variance, lengthscales, n_ls, Kfr, kfr_bytes, stream, true);
 }
 
-static int64_t rbf_bwd_chunk(int64_t N) { return 4096; }
-
 extern "C" size_t mgp_rbf_backward_workspace_bytes(int64_t N, int64_t M, int32_t D) {
-  int dm = D <= 1 ? 1 : D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : 32;
-  const int64_t nch = (N + rbf_bwd_chunk(N) - 1) / rbf_bwd_chunk(N);
-  return (size_t)((nch > 0 ? nch : 1) * (M > 0 ? M : 1) * (1 + 2 * dm)) * sizeof(double);
+  const int64_t nch = stat_bwd_chunks(N);
+  return (size_t)((nch > 0 ? nch : 1) * (M > 0 ? M : 1) * (1 + 2 * dmax_of(D))) * sizeof(double);
 }
 
 extern "C" int mgp_rbf_backward(const float* X, int64_t ldx, const float* Z, int64_t ldz, int64_t N, int64_t M,
@@ -512,48 +273,17 @@ extern "C" int mgp_rbf_backward(const float* X, int64_t ldx, const float* Z, int
   if (!g_ls) return -18;
   if (M == 0) return MGP_OK;
   if (!workspace || workspace_bytes < mgp_rbf_backward_workspace_bytes(N, M, D)) return MGP_ERR_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t chunk = rbf_bwd_chunk(N);
-  const int nch = (int)((N + chunk - 1) / chunk);
-  double* part = (double*)workspace;
-  const float zf = symmetric ? 2.f : 1.f;
-  const dim3 grid((unsigned)((M + 4 * kRbfRows - 1) / (4 * kRbfRows)), (unsigned)(nch > 0 ? nch : 1));
-#define MGP_RBF_BWD_CASE(DM)                                                                                  \
-  if (D <= DM) {                                                                                              \
-    const bool vec = DM >= 4 && ldx % 4 == 0 && ldx >= DM && aligned16(X);                                     \
-    if (nch > 0 && vec)                                                                                       \
-      hipLaunchKernelGGL((rbf_bwd_rows_kernel<DM, true>), grid, dim3(256), 0, s, X, ldx, Z, ldz, N, M, D,       \
-                         variance, lengthscales, n_ls, gK, ldg, chunk, part);                                 \
-    else if (nch > 0)                                                                                         \
-      hipLaunchKernelGGL(rbf_bwd_rows_kernel<DM>, grid, dim3(256), 0, s, X, ldx, Z, ldz, N, M, D, variance,    \
-                         lengthscales, n_ls, gK, ldg, chunk, part);                                           \
-    else                                                                                                      \
-      hipMemsetAsync(part, 0, mgp_rbf_backward_workspace_bytes(N, M, D), s);                                  \
-    if (nch > 1)                                                                                              \
-      hipLaunchKernelGGL(rbf_bwd_fold_kernel, dim3((unsigned)((M * (1 + 2 * DM) + 255) / 256)), dim3(256), 0, s, \
-                         part, nch, M * (1 + 2 * DM));                                                        \
-    hipLaunchKernelGGL(rbf_bwd_finish_kernel<DM>, dim3(1), dim3(256), 0, s, part, 1, M, D, variance,           \
-                       lengthscales, n_ls, zf, accumulate, gZ, ldgz, g_var, g_ls);                            \
-    return launch_status();                                                                                   \
-  }
-  MGP_RBF_BWD_CASE(1)
-  MGP_RBF_BWD_CASE(2)
-  MGP_RBF_BWD_CASE(4)
-  MGP_RBF_BWD_CASE(8)
-  MGP_RBF_BWD_CASE(16)
-  MGP_RBF_BWD_CASE(32)
-#undef MGP_RBF_BWD_CASE
-  return MGP_ERR_UNSUPPORTED;
+  return stat_bwd_launch(FamSE{}, X, ldx, Z, ldz, N, M, D, variance, lengthscales, n_ls, gK, ldg, symmetric, accumulate,
+                         gZ, ldgz, g_var, g_ls, (double*)workspace, (hipStream_t)stream);
 }
 
 static int64_t rbf_bwd_batch_nch(int64_t N) {
-  const int64_t c = rbf_bwd_chunk(N), n = (N + c - 1) / c;
+  const int64_t n = stat_bwd_chunks(N);
   return n > 0 ? n : 1;
 }
 
 extern "C" size_t mgp_rbf_backward_batch_workspace_bytes(int64_t N, int64_t M, int32_t D) {
-  int dm = D <= 1 ? 1 : D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : 32;
-  return (size_t)((rbf_bwd_batch_nch(N) + 1) * (M > 0 ? M : 1) * (1 + 2 * dm)) * sizeof(double);
+  return (size_t)((rbf_bwd_batch_nch(N) + 1) * (M > 0 ? M : 1) * (1 + 2 * dmax_of(D))) * sizeof(double);
 }
 
 extern "C" int mgp_rbf_backward_batch(int32_t batch, const float* X, int64_t ldx, int64_t N,
@@ -601,35 +331,27 @@ extern "C" int mgp_rbf_backward_batch(int32_t batch, const float* X, int64_t ldx
   const size_t per = mgp_rbf_backward_batch_workspace_bytes(N, M, D);
   if (!workspace || workspace_bytes < (size_t)batch * per) return MGP_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  const int64_t chunk = rbf_bwd_chunk(N), slab = (int64_t)(per / sizeof(double));
+  const int64_t chunk = kStatChunk, slab = (int64_t)(per / sizeof(double));
   const int nch = (int)rbf_bwd_batch_nch(N);
   double* ws = (double*)workspace;
   bool zvec = ldz % 4 == 0;
   for (int b = 0; b < batch; ++b) zvec = zvec && aligned16(Z[b]);
-  const dim3 grid((unsigned)((M + 4 * kRbfRows - 1) / (4 * kRbfRows)), (unsigned)(nch + 1), (unsigned)batch);
+  const dim3 grid((unsigned)((M + 4 * kStatRows - 1) / (4 * kStatRows)), (unsigned)(nch + 1), (unsigned)batch);
   // the point loads' form only (dwordx4 or dword): the same values either way
-#define MGP_RBF_BWDB_CASE(DM)                                                                                   \
-  if (D <= DM) {                                                                                                \
-    const bool vec = DM >= 4 && ldx % 4 == 0 && ldx >= DM && aligned16(X) && ldz >= DM && zvec;                  \
-    if (vec)                                                                                                    \
-      hipLaunchKernelGGL((rbf_bwd_rows_batch_kernel<DM, true>), grid, dim3(256), 0, s, X, ldx, N, ldz, M, D,      \
-                         n_ls, lay, ldgf, ldgu, chunk, nch, slab, ws);                                          \
-    else                                                                                                        \
-      hipLaunchKernelGGL((rbf_bwd_rows_batch_kernel<DM, false>), grid, dim3(256), 0, s, X, ldx, N, ldz, M, D,     \
-                         n_ls, lay, ldgf, ldgu, chunk, nch, slab, ws);                                          \
-    if (nch > 1)                                                                                                \
-      hipLaunchKernelGGL(rbf_bwd_fold_kernel, dim3((unsigned)((M * (1 + 2 * DM) + 255) / 256), (unsigned)batch),   \
-                         dim3(256), 0, s, ws, nch, M * (1 + 2 * DM), slab);                                     \
-    hipLaunchKernelGGL(rbf_bwd_finish_batch_kernel<DM>, dim3((unsigned)batch), dim3(256), 0, s, ws, slab, nch, M, \
-                       D, n_ls, lay, accumulate, ldgz);                                                         \
-    return launch_status();                                                                                     \
-  }
-  MGP_RBF_BWDB_CASE(1)
-  MGP_RBF_BWDB_CASE(2)
-  MGP_RBF_BWDB_CASE(4)
-  MGP_RBF_BWDB_CASE(8)
-  MGP_RBF_BWDB_CASE(16)
-  MGP_RBF_BWDB_CASE(32)
-#undef MGP_RBF_BWDB_CASE
-  return MGP_ERR_UNSUPPORTED;
+  return dispatch_dmax(D, [&](auto dm) {
+    constexpr int DM = decltype(dm)::value, NS = 1 + 2 * DM;
+    constexpr bool kVec = DM >= 4;  // below 4 the second launch is the first's instance
+    if (kVec && ldx % 4 == 0 && ldx >= DM && aligned16(X) && ldz >= DM && zvec)
+      hipLaunchKernelGGL((rbf_bwd_rows_batch_kernel<DM, kVec>), grid, dim3(256), 0, s, X, ldx, N, ldz, M, D, n_ls, lay,
+                         ldgf, ldgu, chunk, nch, slab, ws);
+    else
+      hipLaunchKernelGGL((rbf_bwd_rows_batch_kernel<DM, false>), grid, dim3(256), 0, s, X, ldx, N, ldz, M, D, n_ls,
+                         lay, ldgf, ldgu, chunk, nch, slab, ws);
+    if (nch > 1)
+      hipLaunchKernelGGL(stat_bwd_fold_kernel, dim3((unsigned)((M * NS + 255) / 256), (unsigned)batch), dim3(256), 0,
+                         s, ws, nch, M * NS, slab);
+    hipLaunchKernelGGL(rbf_bwd_finish_batch_kernel<DM>, dim3((unsigned)batch), dim3(256), 0, s, ws, slab, nch, M, D,
+                       n_ls, lay, accumulate, ldgz);
+    return launch_status();
+  });
 }

@@ -46,7 +46,7 @@ def _write_problem(path, X, Y, p, z, u):
                                           (65536, 1024, 8, 8, 1.0, 25),    # BASELINE config 3 in full
                                           # K > 16: K4 (mgp_trsm_stats*) stops at 16 experts, so these run
                                           # --front alone, the one chain that takes K <= 32 end to end
-                                          # (D = 17, 32 with lengthscale 0.9 sqrt(D): rbf_kernel<32>)
+                                          # (D = 17, 32 with lengthscale 0.9 sqrt(D): stat_tile_kernel<FamSE, 32>)
                                           (300, 40, 17, 17, 3.71, 3), (300, 70, 32, 32, 5.09, 3)])
 def test_elbo_through_the_c_abi_alone(device, tmp_path, N, M, K, D, ls, S):
     if not os.path.exists(BIN):

@@ -89,7 +89,7 @@ def rbf_case(D, ard, N, M, scale=1.0):
 @pytest.mark.parametrize("ard", [False, True])
 @pytest.mark.parametrize("D", EDGE_D)
 def test_rbf_kuf_kuu_edges(device, D, ard):
-    """rbf_kernel<8 / 16 / 32> at ragged D: N = 1100 crosses the 1024-column tile (a second
+    """stat_tile_kernel<FamSE, 8 / 16 / 32> at ragged D: N = 1100 crosses the 1024-column tile (a second
     column block of 76, the last thread's float4 cut), M = 70 the 64-row tile."""
     from modulatedgps_amd import ops
     N, M = 1100, 70
@@ -192,7 +192,7 @@ BWD_LAYOUTS = [(13, 16), (13, 13), (20, 32), (17, 17), (32, 32), (31, 31)]
 @pytest.mark.parametrize("ard", [False, True])
 @pytest.mark.parametrize("D,ldx", BWD_LAYOUTS)
 def test_rbf_backward_edges(device, D, ldx, ard, sym):
-    """rbf_bwd_rows / finish<16>, <32> against float64 autograd.  D = 13 in rows of 16, D = 20
+    """stat_bwd_rows / finish<FamSE, 16>, <FamSE, 32> against float64 autograd.  D = 13 in rows of 16, D = 20
     in rows of 32 and D = 32 take the dwordx4 point loads (ldx % 4 == 0, ldx >= DMAX); ldx =
     13, 17, 31 the dword loads.  N = 1100: four full 256-point sweeps and a tail of 76 (one
     64-point step and 12 lanes); M = 70: nine 8-row workgroups, the last with 6 rows."""

@@ -140,7 +140,7 @@ def test_kuu_factorisation_bits(device, D, ard):
 @pytest.mark.parametrize("D,ard", CASES, ids=CASE_IDS)
 def test_rbf_kuf_kuu_bits(device, D, ard):
     """mgp_rbf_kuf, mgp_rbf_kuu with its jitter diagonal, and the front's mgp_rbf_kuu_jitter
-    (fixed: rbf_kernel scaled each coordinate before the difference)."""
+    (fixed: the f32 tile kernel scaled each coordinate before the difference)."""
     from modulatedgps_amd import _lib, ops
     var, ls = _hyper(D, ard, device)
 
@@ -165,7 +165,7 @@ def test_rbf_kuf_kuu_bits(device, D, ard):
 @pytest.mark.parametrize("D,ard", CASES, ids=CASE_IDS)
 def test_rbf_backward_bits(device, D, ard):
     """mgp_rbf_backward (Kuf cotangent, and the symmetric Kuu one) and mgp_rbf_backward_batch,
-    the same cotangents given to both calls (already right: rbf_bwd_rows_body differences the
+    the same cotangents given to both calls (already right: FamSE::bwd_point differences the
     raw coordinates)."""
     from modulatedgps_amd import ops
     var, ls = _hyper(D, ard, device)
