@@ -38,7 +38,8 @@
  *      experts K <= 32: K6 and its backward (mgp_elbo_terms*), mgp_relaxed_onehot_sample,
  *        mgp_e_log_p_y, mgp_predict_samples*, mgp_multiclass_predict,
  *        mgp_full_cov_conditional, mgp_mixture_predict / _density_grid, mgp_mixture_score,
- *        mgp_mixture_quantiles (also Q <= 256 levels) and the front's mgp_expert_conditional;
+ *        mgp_mixture_quantiles (also Q <= 256 levels), mgp_mixture_responsibilities,
+ *        mgp_mixture_modes and the front's mgp_expert_conditional;
  *      K unbounded: K5 on given statistics (mgp_expert_conditional_f32 / _x6 / _planes /
  *        _f16*), the image splits, mgp_gauss_kl_white, mgp_predict_epilogue,
  *        mgp_assign_logits, mgp_philox_noise / _normal2; mgp_natgrad_step up to its grid
@@ -893,6 +894,62 @@ int mgp_mixture_quantiles(const float* mu_f, const float* var_f, int64_t ldf, co
                           const float* weights, int64_t N, int32_t K, const float* levels, int32_t Q,
                           float* quantiles, int64_t ldq, mgp_stream_t stream);
 
+/* ---------------------------------------------------------------- mixture assignment and modes (csrc/mixture_assign.hip)
+ * Which expert produced an observation, and the point predictions of the mixture predictive
+ * above, from the latents and the weights [N][K] of mgp_mixture_predict (no noise is drawn
+ * here).  DESIGN "Data association and modes" is the specification.  Conventions of
+ * mgp_mixture_score: latents expert-major [K][ldf >= N]; lik_var [K], weights [N][K] row-major,
+ * Y [N] (device); s_k = sqrt(var_f,k + lik_var_k), t_k = (Y - mu_f,k) / s_k.  No floating-point
+ * atomics and fixed summation orders: two calls return the same bits, and a per-point output
+ * depends neither on N nor on the point's position (a call on a shard returns the bits of the
+ * full call).  Nothing is allocated.
+ *
+ * mgp_mixture_responsibilities: the posterior p(z = k | x, y) in the log domain, the maximum
+ * subtracted.  With a_k = log w_k - log s_k - t_k^2 / 2 (-inf for w_k <= 0):
+ *   resp[n][k] = exp(a_k - logsumexp_j a_j)          [N][ldr >= K] row-major; w_k == 0 gives
+ *                exactly 0; finite and summing to 1 however far Y lies from every expert
+ *   labels[n]  = argmax_k a_k (int32), decided on the a_k, ties to the lowest k
+ *   entropy[n] = logsumexp(a) - sum_k resp_k a_k, terms with resp_k == 0 skipped: the assignment
+ *                entropy in nats (0 for K = 1)
+ *   usage[k]   = sum_n resp[n][k]  (double [K]; deterministic two-stage sum of the float32
+ *                values; the usage of shards adds up): the points each expert explains
+ * A row with no positive weight gives NaN in resp and entropy and the label -1.  Every output
+ * may be NULL.  The workspace (mgp_mixture_responsibilities_workspace_bytes(N, K), also
+ * mgp_workspace_bytes(MGP_OP_MIXTURE_RESPONSIBILITIES, 0, N, K)) is used, and checked, only
+ * when usage is not NULL.
+ * -1 mu_f, -2 var_f, -3 ldf < N, -4 lik_var, -5 weights, -6 Y, -8 K < 1, -10 ldr < K (resp not
+ * NULL); K > 32: MGP_ERR_UNSUPPORTED; all checked before any pointer is read or HIP call made.
+ * N <= 0: MGP_OK after the checks, nothing done. */
+size_t mgp_mixture_responsibilities_workspace_bytes(int64_t N, int32_t K);
+int mgp_mixture_responsibilities(const float* mu_f, const float* var_f, int64_t ldf, const float* lik_var,
+                                 const float* weights, const float* Y, int64_t N, int32_t K, float* resp,
+                                 int64_t ldr, int32_t* labels, float* entropy, double* usage, void* workspace,
+                                 size_t workspace_bytes, mgp_stream_t stream);
+/* The modes (local maxima) of p(y) = sum_k w_k N(y | mu_k, s_k^2) per point: the distinct limits
+ * of hill-climbing p from the expert means mu_k with w_k > 0 (Carreira-Perpinan 2000).  Two
+ * limits that differ by at most 1e-3 min_k s_k are one mode, represented by the one of higher
+ * density.
+ *   modes[n][0 .. count - 1]  in order of decreasing density, ties in ascending y
+ *   mode_density[n][..]       p at the mode; both [N][ldm >= K] row-major, NaN from count[n] to
+ *                             K - 1 (columns from K on are not written)
+ *   count[n]                  int32 in 1 .. K (0 for a row with no positive weight)
+ * The climb of one start steps uphill by the mean-shift step y <- sum_k r_k(y) mu_k / s_k^2 /
+ * sum_k r_k(y) / s_k^2 (r_k(y) evaluated in the log domain) or by half the s_k of the narrowest
+ * expert whose term at y is at least 2^-10 of the largest where that is longer, and where
+ * p'' < 0 by the Newton step on p' if that is shorter; once iterates with p' > 0 and p' < 0
+ * bracket a maximum, the bisection point
+ * replaces an iterate outside the bracket.  It runs in float64 and is rounded to float32 once;
+ * it stops at a step of at most 1e-9 min_k s_k and after at most 100 evaluations of p' per
+ * start: a start that has not converged by then returns its last iterate.  Every output may be
+ * NULL.  No workspace
+ * (mgp_workspace_bytes(MGP_OP_MIXTURE_MODES, ...) is 0).
+ * -1 mu_f, -2 var_f, -3 ldf < N, -4 lik_var, -5 weights, -7 K < 1, -10 ldm < K (modes or
+ * mode_density not NULL); K > 32: MGP_ERR_UNSUPPORTED; all checked before any pointer is read or
+ * HIP call made.  N <= 0: MGP_OK after the checks, nothing done. */
+int mgp_mixture_modes(const float* mu_f, const float* var_f, int64_t ldf, const float* lik_var,
+                      const float* weights, int64_t N, int32_t K, float* modes, float* mode_density, int64_t ldm,
+                      int32_t* count, mgp_stream_t stream);
+
 /* ---------------------------------------------------------------- k-means (csrc/kmeans.hip)
  * scipy.cluster.vq on the device: the inducing-point initialisation of every reference
  * demo, Z = kmeans(Xtrain, num_ind, seed=0)[0] (demos/demo_tf2.py:39).  obs [N][ldo >= D]
@@ -1088,7 +1145,9 @@ enum {
   MGP_OP_FULL_COV_CONDITIONAL = 12,
   MGP_OP_MIXTURE_PREDICT = 13,
   MGP_OP_MIXTURE_SCORE = 14,
-  MGP_OP_PATH_EVAL = 15   /* needs no workspace: 0 */
+  MGP_OP_PATH_EVAL = 15,  /* needs no workspace: 0 */
+  MGP_OP_MIXTURE_RESPONSIBILITIES = 16,
+  MGP_OP_MIXTURE_MODES = 17   /* needs no workspace: 0 */
 };
 size_t mgp_workspace_bytes(int32_t op, int64_t M, int64_t N, int32_t K);
 /* Kuu = K(Z, Z) + jitter I in float32 (covariances.Kuu, models.py:135); same as

@@ -127,6 +127,10 @@ extern "C" size_t mgp_workspace_bytes(int32_t op, int64_t M, int64_t N, int32_t 
       return mgp_mixture_score_workspace_bytes(N, K);
     case MGP_OP_PATH_EVAL:
       return 0;
+    case MGP_OP_MIXTURE_RESPONSIBILITIES:
+      return mgp_mixture_responsibilities_workspace_bytes(N, K);
+    case MGP_OP_MIXTURE_MODES:
+      return 0;
     default:
       return 0;
   }

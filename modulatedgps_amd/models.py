@@ -1459,6 +1459,97 @@ class SMGP(SGP):
         self.check_linalg()
         return float(v.cpu())
 
+    # ------------------------------------------------------------------ data association and modes
+    # Which expert produced an observation -- the posterior p(z = k | x, y) ~ w_k(x) N(y | mu_k,
+    # s_k^2), where predict_assign and predict_mixture_weights give the prior w_k(x) -- and the
+    # point predictions of the mixture predictive, its modes (DESIGN "Data association and
+    # modes").  One conditionals(X), one mgp_mixture_predict for the weights (S, noise_z and seed
+    # as above) and one mgp_mixture_responsibilities or mgp_mixture_modes on them.
+    def _responsibilities(self, Xnew, Ynew, S, want, noise_z=None, seed=None, n_offset=0):
+        if Ynew is None:
+            raise ValueError("Ynew is required")
+        out, (mu_f, var_f, lik_var) = self._mixture(Xnew, S, ("weights",), Y=Ynew, noise_z=noise_z, seed=seed,
+                                                    n_offset=n_offset)
+        Yd = _to_dev(Ynew, self.device).reshape(-1).contiguous()
+        return ops.mixture_responsibilities(mu_f, var_f, lik_var, out["weights"], Yd, want=want)
+
+    def predict_responsibilities_device(self, Xnew, Ynew, S=0, noise_z=None, seed=None):
+        """predict_responsibilities as a float32 device tensor [N, K]."""
+        return self._responsibilities(Xnew, Ynew, S, ("resp",), noise_z=noise_z, seed=seed)["resp"]
+
+    def predict_responsibilities(self, Xnew, Ynew, S=0, noise_z=None, seed=None):
+        """The posterior responsibilities p(z = k | Xnew, Ynew), [N, K] (HostArray, float64):
+        w_k N(Ynew | mu_k, s_k^2) normalised over k in the log domain, so a target far from every
+        expert still gets finite values that sum to 1."""
+        r = self.predict_responsibilities_device(Xnew, Ynew, S, noise_z=noise_z, seed=seed)
+        self.check_linalg()
+        return _host(r)
+
+    def predict_labels_device(self, Xnew, Ynew, S=0, noise_z=None, seed=None):
+        """predict_labels as an int32 device tensor [N]."""
+        return self._responsibilities(Xnew, Ynew, S, ("labels",), noise_z=noise_z, seed=seed)["labels"]
+
+    def predict_labels(self, Xnew, Ynew, S=0, noise_z=None, seed=None):
+        """The expert that most probably produced each observation, int [N] (HostArray): the
+        argmax of the responsibilities, decided on their logarithms, ties to the lowest k."""
+        lab = self.predict_labels_device(Xnew, Ynew, S, noise_z=noise_z, seed=seed)
+        self.check_linalg()
+        return lab.cpu().numpy().astype(np.int64).view(HostArray)
+
+    def predict_assignment_entropy_device(self, Xnew, Ynew, S=0, noise_z=None, seed=None):
+        """predict_assignment_entropy as a float32 device tensor [N]."""
+        return self._responsibilities(Xnew, Ynew, S, ("entropy",), noise_z=noise_z, seed=seed)["entropy"]
+
+    def predict_assignment_entropy(self, Xnew, Ynew, S=0, noise_z=None, seed=None):
+        """The entropy of the responsibilities per point in nats, [N] (HostArray, float64): 0
+        where one expert explains the observation, log K where all do equally."""
+        e = self.predict_assignment_entropy_device(Xnew, Ynew, S, noise_z=noise_z, seed=seed)
+        self.check_linalg()
+        return _host(e)
+
+    def expert_usage_device(self, X, Y, S=0, noise_z=None, seed=None, n_offset=0, process_group=None):
+        """expert_usage as a float64 device tensor [K] (no host sync)."""
+        usage = self._responsibilities(X, Y, S, ("usage",), noise_z=noise_z, seed=seed, n_offset=n_offset)["usage"]
+        if process_group is not None:
+            import torch.distributed as dist
+            dist.all_reduce(usage, op=dist.ReduceOp.SUM, group=process_group)
+        return usage
+
+    def expert_usage(self, X, Y, S=0, noise_z=None, seed=None, n_offset=0, process_group=None):
+        """The effective number of points each expert explains, float64 [K] (HostArray): the
+        responsibilities summed over the points (the values add up to N).  An expert whose
+        count stays near 0 is dead.  n_offset / process_group: sharding over N as in crps (each
+        rank passes its shard; one all-reduce of the K sums; without a group the shards' values
+        add up to the one-call value)."""
+        u = self.expert_usage_device(X, Y, S, noise_z=noise_z, seed=seed, n_offset=n_offset,
+                                     process_group=process_group)
+        self.check_linalg()
+        return _host(u)
+
+    def predict_modes_device(self, Xnew, S=0, noise_z=None, seed=None):
+        """predict_modes as device tensors (float32 [N, K], float32 [N, K], int32 [N])."""
+        out, (mu_f, var_f, lik_var) = self._mixture(Xnew, S, ("weights",), noise_z=noise_z, seed=seed)
+        return ops.mixture_modes(mu_f, var_f, lik_var, out["weights"])
+
+    def predict_modes(self, Xnew, S=0, noise_z=None, seed=None):
+        """The modes of the mixture predictive per point -- its branches, where mean +- 2 sd
+        points between them: (modes [N, K], density [N, K], count [N]) (HostArray; float64,
+        float64, int).  Row n holds its count[n] modes in order of decreasing density, then NaN."""
+        m, d, c = self.predict_modes_device(Xnew, S, noise_z=noise_z, seed=seed)
+        self.check_linalg()
+        return _host(m), _host(d), c.cpu().numpy().astype(np.int64).view(HostArray)
+
+    def predict_map_device(self, Xnew, S=0, noise_z=None, seed=None):
+        """predict_map as a float32 device tensor [N]."""
+        return self.predict_modes_device(Xnew, S, noise_z=noise_z, seed=seed)[0][:, 0]
+
+    def predict_map(self, Xnew, S=0, noise_z=None, seed=None):
+        """The highest mode of the mixture predictive per point, [N] (HostArray, float64):
+        column 0 of predict_modes."""
+        m = self.predict_map_device(Xnew, S, noise_z=noise_z, seed=seed)
+        self.check_linalg()
+        return _host(m)
+
     def sample_paths(self, num_samples, num_features=1024, seed=None):
         """Coherent function samples of the trained mixture (paths.MixturePaths): `.pred` and
         `.assign` are SVGPModified.sample_paths of the two layers, and predict_f(X),

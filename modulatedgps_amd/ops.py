@@ -1328,6 +1328,76 @@ def mixture_quantiles(mu_f, var_f, lik_var, weights, levels, out=None):
     return out
 
 
+# --------------------------------------------------------------------------- mixture assignment and modes
+RESP_OUTPUTS = ("resp", "labels", "entropy", "usage")
+
+
+def _mixture_args(mu_f, var_f, lik_var, weights):
+    """The checks shared by the entries that read mixture_predict's weights -> (K, N, weights)."""
+    _latents_check(mu_f, var_f, "f")
+    K, N = mu_f.shape
+    _check(lik_var, "lik_var"), _check(weights, "weights", 2)
+    if tuple(weights.shape) != (N, K):
+        raise ValueError("weights must be [N, K]")
+    return K, N, weights.contiguous()
+
+
+def mixture_responsibilities(mu_f, var_f, lik_var, weights, Y, want=("resp",), workspace=None, out=None):
+    """The posterior responsibilities p(z = k | x, y) of the mixture predictive at the targets Y
+    (mgp_mixture_responsibilities, csrc/mixture_assign.hip), from mixture_predict's weights
+    [N, K] -> dict of the outputs named in `want`: resp [N, K] (float32; a view of a padded
+    buffer), labels [N] (int32; argmax of the log responsibilities, -1 for a row with no positive
+    weight), entropy [N] (float32, nats) and usage [K] (float64: sum_n resp, the points each
+    expert explains).  out: a dict of an earlier call at the same shapes, written again."""
+    K, N, weights = _mixture_args(mu_f, var_f, lik_var, weights)
+    dev = mu_f.device
+    Y = Y.reshape(-1)
+    _check(Y, "Y")
+    if Y.numel() != N or not Y.is_contiguous():
+        raise ValueError("Y must be contiguous with N elements")
+    unknown = [w for w in want if w not in RESP_OUTPUTS]
+    if unknown:
+        raise ValueError(f"unknown outputs {unknown}; choose from {RESP_OUTPUTS}")
+    spec = {"resp": ((N, K), F32), "labels": ((N,), torch.int32), "entropy": ((N,), F32),
+            "usage": ((K,), torch.float64)}
+    have, out = out or {}, {}
+    for name in want:
+        shape, dtype = spec[name]
+        t = have.get(name)
+        if t is not None:
+            if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or (t.dim() and t.stride(-1) != 1):
+                raise ValueError(f"out[{name!r}] must be a {dtype} tensor of shape {shape} with contiguous rows")
+        elif name == "resp":
+            t = padded(N, K, dev)
+        elif name == "usage" and N == 0:
+            t = torch.zeros(shape, dtype=dtype, device=dev)   # the entry does nothing for N = 0
+        else:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        out[name] = t
+    ldr = _ld(out["resp"]) if "resp" in out and N > 1 else K
+    ws_args = [None, 0]   # only the usage sums need a workspace
+    if "usage" in out:
+        workspace = _workspace("mgp_mixture_responsibilities_workspace_bytes", (N, K), workspace, dev)
+        ws_args = [workspace, workspace.numel()]
+    _lib.call("mgp_mixture_responsibilities", mu_f, var_f, _ld(mu_f), lik_var, weights, Y, N, K, out.get("resp"), ldr,
+              out.get("labels"), out.get("entropy"), out.get("usage"), *ws_args, _stream())
+    return out
+
+
+def mixture_modes(mu_f, var_f, lik_var, weights):
+    """The modes of the mixture predictive per point (mgp_mixture_modes): the distinct limits of
+    hill-climbing from the expert means with a positive weight -> (modes [N, K], density [N, K],
+    count [N] int32).  Row n holds its count[n] modes in order of decreasing density and NaN
+    after them; modes and density are views of padded buffers."""
+    K, N, weights = _mixture_args(mu_f, var_f, lik_var, weights)
+    dev = mu_f.device
+    modes, density = padded(N, K, dev), padded(N, K, dev)
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    ldm = _ld(modes) if N > 1 else K
+    _lib.call("mgp_mixture_modes", mu_f, var_f, _ld(mu_f), lik_var, weights, N, K, modes, density, ldm, count, _stream())
+    return modes, density, count
+
+
 # --------------------------------------------------------------------------- k-means
 I32 = torch.int32
 
