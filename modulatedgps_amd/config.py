@@ -104,15 +104,10 @@ def set_expert_cross(cross):
 #              next step launch's workgroups waited for (32-41 us gaps, round 4 stamps);
 #              with batched K3 only (equal M for both layers), else as "overlap";
 #   "overlap"  K1 and the tril(q_sqrt) images of both layers and the KL on a side
-#              stream beside K3 (round 1-4 default);
-#   "k1a_late" the assign layer's K1 on the side stream after K3, beside the pred
-#              layer's K4 (one K1 beside the chain instead of two);
-#   "k1a_k5"   as k1a_late, but the layers run K4, K5 of the pred layer before the
-#              assign layer's K4, so that K1 runs beside the MFMA-bound K5;
-#   "k1_main"  both K1 on the main stream after K3 (only the small images and
-#              the KL beside the chain);
-#   "serial"   everything on the main stream, K3 alone on the chip.
-STEP_SCHEDULES = ("k1_in_k3", "overlap", "k1a_late", "k1a_k5", "k1_main", "serial")
+#              stream beside K3 (round 1-4 default; what the step itself falls back to);
+#   "serial"   everything on the main stream, K3 alone on the chip (the reference that a
+#              cross-stream race would differ from, tests/test_gpu_schedules.py).
+STEP_SCHEDULES = ("k1_in_k3", "overlap", "serial")
 
 
 def step_schedule():

@@ -34,7 +34,7 @@ inputs, predict_y) are returned as broadcast views of that single result.
 Compute dtype is float32 on the device; the parity tolerances against the
 float64 reference semantics are stated in tests/.
 """
-import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -45,25 +45,16 @@ from .config import (conditional_mode, default_device, default_jitter, expert_cr
                      forward_image_format, step_schedule)
 
 # both layers' K4, and both layers' K5, in one launch each in the step (False: one launch
-# per layer and kernel; A/B probes only)
+# per layer and kernel, the reference of tests/test_gpu_properties.py's bit-for-bit test)
 _K4_BATCHED = True
-# the training forward's colnorm_max (the C_k images' bound) on the side stream beside K3
-# (False: on the main stream right before K5; A/B probes only)
-_COLMAX_SIDE = True
 # split-f16: both layers' tril(q_sqrt) images and KL terms by mgp_qsqrt_images_kl_f16_batch
-# (False: mgp_split_lower_f16 + mgp_gauss_kl_white per layer; A/B probes only)
+# (False: mgp_split_lower_f16 + mgp_gauss_kl_white per layer, the same test's reference)
 _QS_BATCH = True
 # k1_in_k3 carries K1's image blocks on the step launches' idle CUs at one 512-thread
 # workgroup per CU; past this image size (N * M) the blocks outlast the chain's steps
 # (BASELINE c5, N * M = 2^29: K3 2.15 -> 5.78 ms) and K1 runs on the side stream instead
 # (schedule overlap, bit-identical)
 _K1_IN_K3_MAX_NM = 1 << 27
-_TAIL_BATCH = True   # both layers' Cholesky / RBF backward in one batch each (elbo_and_grad)
-_RBF_NO_FILL = True  # the batched RBF backward overwrites gZ / g_ls (False: zero fills + accumulate; A/B only)
-# training: the q_sqrt-only launches of the C-images backward (L_k's image, L_k^T) on the
-# side stream beside K3 (mgp_conditional_backward_prep_f16c; False: inside the backward)
-_COND_PREP = True
-_T_BOUND = True   # the C-images backward takes max |LinvT| from K3's bounded L^-T images (A/B: False)
 
 # The training step keeps each layer's C_k = L_k^T A images for the backward
 # (mgp_conditional_backward_f16c) while both layers' sets fit in this fraction of the
@@ -637,6 +628,42 @@ class SGP:
         return ym[None].expand(S, *ym.shape), yv[None].expand(S, *yv.shape)
 
 
+class _Buffers(dict):
+    """One cached buffer set of SMGP._buffers: name -> tensor.  Beside the tensors it names what
+    the set was sized for -- every launch decision that follows from the layers' shapes and
+    kernels, the config and `train` alone -- so that SMGP._plan reads booleans and nothing asks
+    whether a key exists.  layer: per layer ("f" pred, "a" assign) the `bufs` mapping that the
+    SVGPModified stage methods take (absent buffers are None)."""
+    __slots__ = ("train", "x6", "fmt", "batched_k3", "pairable", "q_batchable", "c_images", "layer")
+
+
+class _StepPlan(NamedTuple):
+    """What one SMGP step launches and where: every decision, resolved once at the top of the
+    step by SMGP._plan (rebuilt each call: the config and the module flags may change between
+    calls on one model).  The stage methods read these and decide nothing themselves."""
+    train: bool       # the training forward: K3 keeps L, K4 the f32 A
+    x6: bool          # the chain runs on fragment images (conditional mode "x6"), else on the exact-f32 MFMA
+    fmt: str          # the images' format, "f16" or "x6" (config.forward_image_format)
+    sched: str        # the schedule that runs: config.step_schedule(), or "overlap" where it cannot
+    batched_k3: bool  # one K3 sweep factorises both layers
+    bounded: bool     # K3 writes max |LinvT| into the L^-T images' trailers; the split and the backward read it
+    tfr_pair: bool    # both layers' L^-T images in one launch (bit-identical to two)
+    q_batch: bool     # both layers' tril(q_sqrt) images and KL terms in one batch entry
+    paired: bool      # both layers' K4 in one launch, and both layers' K5 in one
+    c_images: bool    # K5 keeps the C_k images for the backward, whose q_sqrt-only prep runs beside K3
+    tail_paired: bool  # both layers' Cholesky backward in one launch, and their RBF backward in one
+
+
+class _StepState(NamedTuple):
+    """What a step's forward hands to its backward: the plan it ran under, its buffer set and
+    input, and per layer ("f", "a") K3's factors (L only in training)."""
+    plan: _StepPlan
+    b: _Buffers
+    X: torch.Tensor
+    L: dict
+    LinvT: dict
+
+
 class SMGP(SGP):
     """Mixture of Gaussian processes (models.py:44-103)."""
 
@@ -672,7 +699,8 @@ class SMGP(SGP):
         a = None if x6 else ops.padded(Mx, N, dev)
         st = ops.padded(2 * T * (K + 1), N, dev)  # per layer (the layers' K4 may run concurrently)
         cond = ops.padded(4 * K, N, dev)          # mu_f, var_f, mu_a, var_a
-        b = {
+        fmt = forward_image_format(train)
+        b = _Buffers({
             "Kuf_f": None if x6 else kuf[:Mf], "Kuf_a": None if x6 else kuf[:Ma],
             "A_f": None if x6 else a[:Mf], "A_a": None if x6 else a[:Ma],
             "stats_f": st[:ops.stats_tiles(Mf) * (K + 1)].unflatten(0, (-1, K + 1)),
@@ -681,16 +709,25 @@ class SMGP(SGP):
             "var_a": cond[3 * K:4 * K],
             "kl": torch.empty(2, dtype=torch.float64, device=dev),
             "data_sum": torch.empty(1, dtype=torch.float64, device=dev),
-            "elbo": torch.empty((), dtype=torch.float32, device=dev),
             "elbo64": torch.empty((), dtype=torch.float64, device=dev),
             "ws_expert": torch.empty(max(ops.expert_workspace_bytes(Mx, N, K),
                                          ops.expert_x6_workspace_bytes(Mx, N, K)), dtype=torch.uint8,
                                      device=dev),
-        }
-        if x6 and Mf == Ma and forward_image_format(train) == "f16" and expert_cross() == "f16":
-            # the second layer's K5 workspace, only where both layers' K5 can run as one
-            # launch (split-f16 images with f16 cross terms, equal M)
-            b["ws_expert2"] = torch.empty_like(b["ws_expert"])
+        })
+        b.train, b.x6, b.fmt = bool(train), x6, fmt
+        # both layers' K4, and both layers' K5, can run as one launch each: split-f16 images
+        # with f16 cross terms, equal M (mgp_trsm_stats_f16_batch, mgp_expert_conditional_f16_batch)
+        b.pairable = x6 and Mf == Ma and fmt == "f16" and expert_cross() == "f16"
+        if b.pairable:
+            b["ws_expert2"] = torch.empty_like(b["ws_expert"])   # the second layer's K5 workspace
+        # both layers' tril(q_sqrt) images and KL terms can come from the batch entry
+        # (mgp_qsqrt_images_kl_f16_batch): split-f16 images, equal q_mu shapes
+        b.q_batchable = x6 and fmt == "f16" and Mf == Ma
+        if b.q_batchable:
+            b["qs_ws"] = torch.empty(2 * ops._lib.load().mgp_qsqrt_workspace_bytes(Mf, K), dtype=torch.uint8,
+                                     device=dev)
+            # prediction: the images are wanted, the KL values are not
+            b["kl_scratch"] = torch.empty(2, dtype=torch.float64, device=dev)
         if x6:  # split-bf16 images: Kuf / tril(q_sqrt) per layer (built on the side
             # stream while K3 runs), A and L^-T shared by the layers (processed in turn)
             for L in ("f", "a"):
@@ -699,15 +736,17 @@ class SMGP(SGP):
             for L in ("f", "a"):  # per layer: the two layers' K4 run concurrently
                 b["Afr_" + L] = torch.empty(ops.x6_cols_bytes(Mx, N), dtype=torch.uint8, device=dev)
                 b["Tfr_" + L] = torch.empty(ops.x6_lower_bytes(Mx, 1), dtype=torch.uint8, device=dev)
-        b["x6"] = x6
-        if Mf == Ma and self.pred_layer.Z.shape[1] == self.assign_layer.Z.shape[1] and self._both_se():
-            # (the two-layer K3 builds SquaredExponential Kuu; a Matern layer factorises on its own)
+        # one K3 sweep for both layers: equal M and D (the two-layer K3 builds
+        # SquaredExponential Kuu; a Matern layer factorises on its own)
+        b.batched_k3 = (Mf == Ma and self.pred_layer.Z.shape[1] == self.assign_layer.Z.shape[1]
+                        and self._both_se())
+        if b.batched_k3:
             b["LinvT2"] = ops.padded(Mf, Mf, dev, batch=2)
-        b["train"] = bool(train)
+        b.c_images = False
         if train:
             if not x6:
                 raise NotImplementedError("the training step runs on the x6 conditional path")
-            if "LinvT2" in b:
+            if b.batched_k3:
                 b["L2"] = ops.padded(Mf, Mf, dev, batch=2)
             for L, M in (("f", Mf), ("a", Ma)):  # kept for the backward pass
                 b["A32_" + L] = ops.padded(M, N, dev)
@@ -715,7 +754,8 @@ class SMGP(SGP):
             cb = ops.c_images_bytes(Mx, N, K)
             limit = (C_IMAGES_MAX_BYTES if C_IMAGES_MAX_BYTES is not None else
                      C_IMAGES_HBM_FRACTION * torch.cuda.get_device_properties(dev).total_memory / 2)
-            if forward_image_format(True) == "f16" and expert_cross() == "f16" and cb <= limit:
+            b.c_images = fmt == "f16" and expert_cross() == "f16" and cb <= limit
+            if b.c_images:
                 for L in ("f", "a"):  # K5 writes C_k per expert; the backward reads them
                     b["Cfr_" + L] = torch.empty(cb, dtype=torch.uint8, device=dev)
                     b["colmax_" + L] = torch.empty(1, dtype=torch.float32, device=dev)
@@ -723,47 +763,73 @@ class SMGP(SGP):
                                                   dtype=torch.uint8, device=dev)
             b["ws_cbwd"] = torch.empty(ops.conditional_backward_workspace_bytes(Mx, N, K), dtype=torch.uint8,
                                        device=dev)
+        b.layer = {L: {"Kuf": b["Kuf_" + L], "A": b["A_" + L], "stats": b["stats_" + L], "fmean": b["mu_" + L],
+                       "fvar": b["var_" + L], "ws_expert": b["ws_expert"],
+                       "Afr": b["Afr_" + L] if x6 else None, "Tfr": b["Tfr_" + L] if x6 else None,
+                       "A32": b["A32_" + L] if train else None,
+                       "c_out": (b["Cfr_" + L], b["colmax_" + L]) if b.c_images else None} for L in ("f", "a")}
         self._bufs[key] = b
         return b
 
-    def _factorise(self, b, prep_event=None, tfr_bounds=False, kuf=None):
-        """Kuu of both layers and their batched Cholesky + inverse (one K3 sweep).
-        Training buffers also keep L (b["L_f"], b["L_a"]) for the backward pass.
-        prep_event: recorded once Kuu is built (batched path only; else after K3).
-        tfr_bounds: K3 also writes max |LinvT| into the L^-T split-f16 images'
-        trailers (b["Tfr_f"], b["Tfr_a"]; batched path), for bounded splits.
-        kuf: (X, fmt) -- K3's step launches also write both layers' Kuf images
-        (b["Kfr_f"], b["Kfr_a"]; batched path, schedule "k1_in_k3")."""
+    def _layers(self):
+        return (("f", self.pred_layer), ("a", self.assign_layer))
+
+    def _plan(self, b, X):
+        """The launch plan of a step on buffer set b and input X (already through kernel._x)."""
         pf, pa = self.pred_layer, self.assign_layer
-        train = b.get("train", False)
-        if "LinvT2" in b:
+        # the schedules order the image chain's work; the exact-f32 mode has one order
+        sched = step_schedule() if b.x6 else "overlap"
+        # k1_in_k3: both layers' K1 as a side job of the batched K3's step launches, which read
+        # X as given (neither kernel converts it) and carry K1 only up to _K1_IN_K3_MAX_NM;
+        # else K1 runs on the side stream as in overlap (bit-identical)
+        if sched == "k1_in_k3" and not (b.batched_k3 and pf.kernel._x(X) is X and pa.kernel._x(X) is X
+                                        and X.shape[0] * pf.num_inducing <= _K1_IN_K3_MAX_NM):
+            sched = "overlap"
+        # split-f16 L^-T images: K3 folds their scale bound (max |LinvT|) into its
+        # writes of the inverse, so the split needs no reduction launches
+        bounded = b.x6 and b.batched_k3 and b.fmt == "f16"
+        return _StepPlan(
+            train=b.train, x6=b.x6, fmt=b.fmt, sched=sched, batched_k3=b.batched_k3,
+            bounded=bounded, tfr_pair=bounded and _K4_BATCHED,
+            # three launches (mgp_qsqrt_images_kl_f16_batch) instead of five per layer, beside
+            # K3's chain; the batch entry also needs equal q_mu leading dimensions and q_sqrt
+            # ld / stride(0), else the per-layer launches run
+            q_batch=(_QS_BATCH and b.q_batchable and pf.q_mu.stride() == pa.q_mu.stride()
+                     and pf.q_sqrt.stride() == pa.q_sqrt.stride()),
+            # bit-identical to two launches: one kernel tail and dispatch-round boundary fewer
+            # (~25 us, measured).  K5 pairs whenever K4 does: its second workspace exists under
+            # the same condition, and both layers keep or drop their C_k images together
+            paired=_K4_BATCHED and b.pairable,
+            c_images=b.c_images,
+            # with matching shapes (mgp_chol_backward_batch, mgp_rbf_backward_batch)
+            tail_paired=b.train and self._tail_batchable())
+
+    def _factorise(self, plan, b, X, prep_event):
+        """Kuu of both layers and their Cholesky + inverse: per layer ("f", "a") L (training
+        only: kept for the backward pass, else None) and (L^-1)^T, as two dicts.
+        Batched K3 (one sweep for both layers): prep_event is recorded once Kuu is built (else
+        after K3); plan.bounded: K3 also writes max |LinvT| into the L^-T split-f16 images'
+        trailers (b["Tfr_f"], b["Tfr_a"]), for bounded splits; schedule k1_in_k3: its step
+        launches also write both layers' Kuf images (b["Kfr_f"], b["Kfr_a"])."""
+        pf, pa = self.pred_layer, self.assign_layer
+        if plan.batched_k3:
             if pf.Z.stride(0) != pa.Z.stride(0):
                 pa.Z = pa.Z.contiguous()
                 pf.Z = pf.Z.contiguous()
             Lo, LinvT, info = ops.kuu_potrf_trtri(
                 [pf.Z, pa.Z], [pf.kernel.variance, pa.kernel.variance],
                 [pf.kernel.lengthscales, pa.kernel.lengthscales], default_jitter(), LinvT=b["LinvT2"],
-                L=b.get("L2"), want_L=train, prep_event=prep_event,
-                tfr_bound_images=[b["Tfr_f"], b["Tfr_a"]] if tfr_bounds else None,
-                kuf=(kuf[0], [b["Kfr_f"], b["Kfr_a"]], kuf[1]) if kuf is not None else None)
+                L=b["L2"] if plan.train else None, want_L=plan.train, prep_event=prep_event,
+                tfr_bound_images=[b["Tfr_f"], b["Tfr_a"]] if plan.bounded else None,
+                kuf=(X, [b["Kfr_f"], b["Kfr_a"]], plan.fmt) if plan.sched == "k1_in_k3" else None)
             self.last_info = info
-            if train:
-                b["L_f"], b["L_a"] = Lo[0], Lo[1]
-            b["LinvT_f"], b["LinvT_a"] = LinvT[0], LinvT[1]
-            return LinvT[0], LinvT[1]
-        outs = []
-        infos = []
-        for name, layer in (("f", pf), ("a", pa)):
-            Lo, LinvT, info = layer.factorise(want_L=train)
-            outs.append(LinvT[0])
-            infos.append(info)
-            if train:
-                b["L_" + name] = Lo[0]
-            b["LinvT_" + name] = LinvT[0]
-        self.last_info = torch.cat(infos)
+            return dict(zip("fa", Lo if plan.train else (None, None))), dict(zip("fa", LinvT))
+        outs = [layer.factorise(want_L=plan.train) for _, layer in self._layers()]
+        self.last_info = torch.cat([info for *_, info in outs])
         if prep_event is not None:
             prep_event.record()
-        return outs[0], outs[1]
+        return ({n: Lo[0] if plan.train else None for n, (Lo, _, _) in zip("fa", outs)},
+                {n: LinvT[0] for n, (_, LinvT, _) in zip("fa", outs)})
 
     def _both_se(self):
         """Both layers on SquaredExponential kernels: what the two-layer and fused launches
@@ -790,183 +856,121 @@ class SMGP(SGP):
         latency-bound K3 sweep, which occupies only a few CUs.  They start once
         K3 has built Kuu (its prep event): launched beside the build, K1's 4096
         workgroups starve it (101 us instead of ~20)."""
+        b = self._conditionals(X, timing, kl_out, train).b
+        return b["mu_f"], b["var_f"], b["mu_a"], b["var_a"]
+
+    def _conditionals(self, X, timing, kl_out, train):
+        """conditionals' work; the results are in the buffer set of the returned _StepState."""
         ops.check_conditional_experts(self.K)
         X = self.pred_layer.kernel._x(X)
-        N = X.shape[0]
-        b = self._buffers(N, train)
-        layers = (("f", self.pred_layer), ("a", self.assign_layer))
-        images = {}
-        fmt = forward_image_format(train)
-        prep = None
-        if b["x6"]:
-            main = torch.cuda.current_stream(self.device)
-            side = self._side_stream()
-            prep = self._prep_event()
-        # split-f16 L^-T images: K3 folds their scale bound (max |LinvT|) into its
-        # writes of the inverse, so the split needs no reduction launches
-        bounded = b["x6"] and "Tfr_a" in b and "LinvT2" in b and fmt == "f16"
-        b["lt_bounded"] = bounded   # the backward takes max |LinvT| from the Tfr trailers
-        sched = step_schedule() if (b["x6"] and "Tfr_a" in b) else "overlap"
-        # schedule k1_in_k3: both layers' K1 as a side job of K3's step launches (batched K3)
-        k1_in_k3 = (sched == "k1_in_k3" and "LinvT2" in b and self.pred_layer.kernel._x(X) is X
-                    and self.assign_layer.kernel._x(X) is X
-                    and N * self.pred_layer.num_inducing <= _K1_IN_K3_MAX_NM)
-        if sched == "k1_in_k3" and not k1_in_k3:
-            sched = "overlap"
+        b = self._buffers(X.shape[0], train)
+        plan = self._plan(b, X)
+        self.layers_per_launch = 2 if plan.paired else 1   # K4 / K5 launches cover this many layers
+        prep = self._prep_event() if plan.x6 else None
         with _Stage(timing, "kuu_chol"):
-            LinvT_f, LinvT_a = self._factorise(b, prep_event=prep, tfr_bounds=bounded,
-                                               kuf=(X, fmt) if k1_in_k3 else None)
-        Tfr = {}
-        if b["x6"] and "Tfr_a" in b:
-            # L^-T images straight after K3 on its stream (no cross-stream wait in front)
-            with _Stage(timing, "split_tri"):
-                if bounded and _K4_BATCHED:   # both layers' L^-T images in one launch (bit-identical)
-                    Tfr["f"], Tfr["a"] = ops.split_upper_f16_bounded_batch(b["LinvT2"], [b["Tfr_f"], b["Tfr_a"]])
-                else:
-                    for L, lt in (("f", LinvT_f), ("a", LinvT_a)):
-                        Tfr[L] = ops.split_upper_x6(lt, out=b["Tfr_" + L], fmt=fmt, bounded=bounded)
-        late = {"k1_in_k3": (), "overlap": (), "k1a_late": ("a",), "k1a_k5": ("a",), "k1_main": ("f", "a"),
-                "serial": ("f", "a")}[sched]
-        if b["x6"]:
-            pf, pa = self.pred_layer, self.assign_layer
-            # split-f16: both layers' tril(q_sqrt) images and KL terms in three launches
-            # (mgp_qsqrt_images_kl_f16_batch) instead of five per layer, beside K3's chain
-            # (the batch entry also needs equal q_mu leading dimensions and q_sqrt ld / stride(0),
-            # else the per-layer launches run)
-            q_batch = (_QS_BATCH and fmt == "f16" and pf.q_mu.shape == pa.q_mu.shape and "Lfr_f" in b
-                       and pf.q_mu.stride() == pa.q_mu.stride()
-                       and pf.q_sqrt.stride() == pa.q_sqrt.stride())
-
-            def side_work():
-                for L, layer in layers:
-                    X_ = layer.kernel._x(X)
-                    if L not in late and not k1_in_k3:
-                        with _Stage(timing, "rbf_kuf"):
-                            layer.kernel.kuf_image(X_, layer.Z, out=b["Kfr_" + L], fmt=fmt)
-                    with _Stage(timing, "split_tri"):
-                        if not q_batch:
-                            ops.split_lower_x6(layer.q_sqrt, out=b["Lfr_" + L], fmt=fmt)
-                        if _COLMAX_SIDE and "colmax_" + L in b:   # training: the C_k bound, off the K3 -> K5 path
-                            ops.colnorm_max(layer.q_sqrt, out=b["colmax_" + L])
-                    images[L] = (b["Kfr_" + L], b["Lfr_" + L])
-                if q_batch:
-                    if kl_out is not None:
-                        kls = [kl_out[0:1], kl_out[1:2]]
-                    else:   # prediction: the images are wanted, the KL values are not
-                        if "kl_scratch" not in b:
-                            b["kl_scratch"] = torch.empty(2, dtype=torch.float64, device=X.device)
-                        kls = [b["kl_scratch"][0:1], b["kl_scratch"][1:2]]
-                    if "qs_ws" not in b:
-                        M, K = pf.q_mu.shape
-                        b["qs_ws"] = torch.empty(2 * ops._lib.load().mgp_qsqrt_workspace_bytes(M, K),
-                                                 dtype=torch.uint8, device=X.device)
-                    with _Stage(timing, "split_tri"):
-                        ops.qsqrt_images_kl_f16_batch([pf.q_mu, pa.q_mu], [pf.q_sqrt, pa.q_sqrt],
-                                                      [b["Lfr_f"], b["Lfr_a"]], kls, workspace=b["qs_ws"])
-                elif kl_out is not None:
-                    with _Stage(timing, "gauss_kl"):
-                        self.pred_layer.prior_kl(out=kl_out[0:1])
-                        self.assign_layer.prior_kl(out=kl_out[1:2])
-                b["cprep_done"] = False
-                if train and _COND_PREP and fmt == "f16" and "cprep_a" in b:
-                    # the backward's q_sqrt-only launches, on the forward's L_k image bounds
-                    with _Stage(timing, "split_tri"):
-                        for L, layer in layers:
-                            ops.conditional_backward_prep(
-                                layer.q_sqrt, ops.image_bound(b["Lfr_" + L], layer.num_inducing,
-                                                              K=layer.num_latent_gps), out=b["cprep_" + L])
-                    b["cprep_done"] = True
-            if sched == "serial":
-                side_work()
-            else:
-                side.wait_event(prep)   # after Kuu's build (and so after everything before K3 on main)
-                with torch.cuda.stream(side):
-                    side_work()
-                main.wait_stream(side)
-
-            def kuf_late(L):   # a K1 kept off the chain's window (schedules k1a_late, k1_main, serial)
-                layer = self.pred_layer if L == "f" else self.assign_layer
-                with _Stage(timing, "rbf_kuf"):
-                    layer.kernel.kuf_image(layer.kernel._x(X), layer.Z, out=b["Kfr_" + L], fmt=fmt)
-        LinvT = {"f": LinvT_f, "a": LinvT_a}
-        bufs = {L: {"Kuf": b["Kuf_" + L], "A": b["A_" + L], "stats": b["stats_" + L],
-                    "fmean": b["mu_" + L], "fvar": b["var_" + L], "ws_expert": b["ws_expert"],
-                    "Afr": b.get("Afr_" + L, b.get("Afr")), "Tfr": b.get("Tfr_" + L, b.get("Tfr")),
-                    "A32": b.get("A32_" + L),
-                    "c_out": (b["Cfr_" + L], b["colmax_" + L]) if "Cfr_" + L in b else None} for L, _ in layers}
-        if b["x6"] and "Tfr_a" in b:
-            # both layers' K4 then both K5 in stream order on the main stream: the
-            # matrix-core kernels fill the chip alone, and a cross-stream hand-off
-            # costs 10-25 us of idle GPU per wait (measured)
-            pf, pa = self.pred_layer, self.assign_layer
-            k1a_ev = None
-
-            def side_kuf_a():   # the assign layer's K1 on the side stream from here on
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    kuf_late("a")
-                ev = torch.cuda.Event()
-                ev.record(side)
-                return ev
-            if sched == "k1a_late":          # beside the pred layer's K4
-                k1a_ev = side_kuf_a()
-            elif sched in ("k1_main", "serial"):
-                kuf_late("f")
-                kuf_late("a")
-            bf, ba = bufs["f"], bufs["a"]
-            # both layers' K4 in one launch (mgp_trsm_stats_f16_batch, bit-identical to
-            # two): one kernel tail and dispatch-round boundary fewer (~25 us, measured)
-            batched = (_K4_BATCHED and sched in ("k1_in_k3", "overlap", "k1_main", "serial") and fmt == "f16"
-                       and expert_cross() == "f16"
-                       and pf.num_inducing == pa.num_inducing and pf.num_latent_gps == pa.num_latent_gps
-                       and all(x.get("Afr") is not None and x.get("stats") is not None for x in (bf, ba))
-                       and bf["Afr"].data_ptr() != ba["Afr"].data_ptr()
-                       and (bf.get("A32") is None) == (ba.get("A32") is None))
-            self.layers_per_launch = 2 if batched else 1   # K4 / K5 launches cover this many layers
-            if batched:
-                with _Stage(timing, "trsm_stats"):
-                    (Afr_f, st_f), (Afr_a, st_a) = ops.trsm_stats_f16_batch(
-                        [Tfr["f"], Tfr["a"]], [images["f"][0], images["a"][0]], [pf.q_mu, pa.q_mu],
-                        pf.num_inducing, N, [bf["Afr"], ba["Afr"]], [bf["stats"], ba["stats"]],
-                        [pf.kernel.variance, pa.kernel.variance],
-                        As=[bf["A32"], ba["A32"]] if bf.get("A32") is not None else None)
-            else:
-                Afr_f, st_f = pf.x6_trsm(N, LinvT["f"], images["f"][0], bf, timing, fmt, Tfr=Tfr["f"])
-            if sched == "k1a_k5":            # beside the pred layer's K5
-                k1a_ev = side_kuf_a()
-                pf.x6_expert(N, Afr_f, images["f"][1], st_f, bufs["f"], timing, fmt, colmax_ready=_COLMAX_SIDE)
-            if k1a_ev is not None:
-                main.wait_event(k1a_ev)
-            if not batched:
-                Afr_a, st_a = pa.x6_trsm(N, LinvT["a"], images["a"][0], ba, timing, fmt, Tfr=Tfr["a"])
-            if batched and "ws_expert2" in b and (bf.get("c_out") is None) == (ba.get("c_out") is None):
-                # both layers' K5 in one launch too (mgp_expert_conditional_f16_batch, bit-identical)
-                with _Stage(timing, "expert_cond"):
-                    c_outs = None
-                    if bf.get("c_out") is not None and ba.get("c_out") is not None:
-                        c_outs = [bf["c_out"], ba["c_out"]]   # bounds from the side stream's colnorm_max
-                        if not _COLMAX_SIDE:
-                            ops.colnorm_max(pf.q_sqrt, out=bf["c_out"][1])
-                            ops.colnorm_max(pa.q_sqrt, out=ba["c_out"][1])
-                    ops.expert_conditional_f16_batch(
-                        [Afr_f, Afr_a], [images["f"][1], images["a"][1]], [st_f, st_a],
-                        [pf.kernel.variance, pa.kernel.variance], pf.num_inducing, N, pf.num_latent_gps,
-                        [bf["fmean"], ba["fmean"]], [bf["fvar"], ba["fvar"]], [b["ws_expert"], b["ws_expert2"]],
-                        c_outs=c_outs)
-            else:
-                if sched != "k1a_k5":
-                    pf.x6_expert(N, Afr_f, images["f"][1], st_f, bufs["f"], timing, fmt, colmax_ready=_COLMAX_SIDE)
-                pa.x6_expert(N, Afr_a, images["a"][1], st_a, bufs["a"], timing, fmt, colmax_ready=_COLMAX_SIDE)
+            L, LinvT = self._factorise(plan, b, X, prep)
+        st = _StepState(plan, b, X, L, LinvT)
+        if not plan.x6:
+            self._chain_f32(st, timing, kl_out)
+            return st
+        # L^-T images straight after K3 on its stream (no cross-stream wait in front)
+        self._linvt_images(st, timing)
+        if plan.sched == "serial":   # everything on the main stream, K1 kept off K3's window
+            self._side_work(st, timing, kl_out)
+            for L, layer in self._layers():
+                self._kuf_image(st, L, layer, timing)
         else:
-            for L, layer in layers:
-                if L in late:
-                    kuf_late(L)
-                layer.conditional_kn(X, LinvT[L], bufs=bufs[L], timing=timing, images=images.get(L), fmt=fmt)
-        if kl_out is not None and not b["x6"]:
+            main, side = torch.cuda.current_stream(self.device), self._side_stream()
+            side.wait_event(prep)   # after Kuu's build (and so after everything before K3 on main)
+            with torch.cuda.stream(side):
+                self._side_work(st, timing, kl_out)
+            main.wait_stream(side)
+        self._k4_k5(st, timing)
+        return st
+
+    def _kuf_image(self, st, L, layer, timing):
+        """K1 of one layer on the current stream: its Kuf image."""
+        with _Stage(timing, "rbf_kuf"):
+            layer.kernel.kuf_image(layer.kernel._x(st.X), layer.Z, out=st.b["Kfr_" + L], fmt=st.plan.fmt)
+
+    def _linvt_images(self, st, timing):
+        """Both layers' L^-T images for K4 (x6 mode), on K3's stream."""
+        plan, b = st.plan, st.b
+        with _Stage(timing, "split_tri"):
+            if plan.tfr_pair:
+                ops.split_upper_f16_bounded_batch(b["LinvT2"], [b["Tfr_f"], b["Tfr_a"]])
+            else:
+                for L, _ in self._layers():
+                    ops.split_upper_x6(st.LinvT[L], out=b["Tfr_" + L], fmt=plan.fmt, bounded=plan.bounded)
+
+    def _side_work(self, st, timing, kl_out):
+        """The Cholesky-independent work of an x6 step, on the current stream (the side stream
+        beside K3; schedule serial: the main stream): K1 (schedule overlap), the tril(q_sqrt)
+        images, both KL terms when kl_out is given, and in training the C_k images' bound and
+        the backward's q_sqrt-only launches."""
+        plan, b = st.plan, st.b
+        pf, pa = self.pred_layer, self.assign_layer
+        for L, layer in self._layers():
+            if plan.sched == "overlap":
+                self._kuf_image(st, L, layer, timing)
+            with _Stage(timing, "split_tri"):
+                if not plan.q_batch:
+                    ops.split_lower_x6(layer.q_sqrt, out=b["Lfr_" + L], fmt=plan.fmt)
+                if plan.c_images:   # colnorm_max of q_sqrt, off the K3 -> K5 path
+                    ops.colnorm_max(layer.q_sqrt, out=b["colmax_" + L])
+        if plan.q_batch:
+            kl = kl_out if kl_out is not None else b["kl_scratch"]
+            with _Stage(timing, "split_tri"):
+                ops.qsqrt_images_kl_f16_batch([pf.q_mu, pa.q_mu], [pf.q_sqrt, pa.q_sqrt],
+                                              [b["Lfr_f"], b["Lfr_a"]], [kl[0:1], kl[1:2]], workspace=b["qs_ws"])
+        elif kl_out is not None:
+            with _Stage(timing, "gauss_kl"):
+                pf.prior_kl(out=kl_out[0:1])
+                pa.prior_kl(out=kl_out[1:2])
+        if plan.c_images:
+            # the backward's q_sqrt-only launches, on the forward's L_k image bounds
+            with _Stage(timing, "split_tri"):
+                for L, layer in self._layers():
+                    ops.conditional_backward_prep(
+                        layer.q_sqrt, ops.image_bound(b["Lfr_" + L], layer.num_inducing,
+                                                      K=layer.num_latent_gps), out=b["cprep_" + L])
+
+    def _k4_k5(self, st, timing):
+        """Both layers' K4 then both K5 in stream order on the main stream (x6 mode): the
+        matrix-core kernels fill the chip alone, and a cross-stream hand-off costs 10-25 us
+        of idle GPU per wait (measured).  plan.paired: one launch for both layers' K4 and one
+        for their K5; else one per layer and kernel."""
+        plan, b, N = st.plan, st.b, st.X.shape[0]
+        pf, pa = self.pred_layer, self.assign_layer
+        bf, ba = b.layer["f"], b.layer["a"]
+        if not plan.paired:
+            k4 = [layer.x6_trsm(N, st.LinvT[L], b["Kfr_" + L], b.layer[L], timing, plan.fmt, Tfr=b["Tfr_" + L])
+                  for L, layer in self._layers()]
+            for (L, layer), (Afr, stats) in zip(self._layers(), k4):   # (the C_k bounds: _side_work's)
+                layer.x6_expert(N, Afr, b["Lfr_" + L], stats, b.layer[L], timing, plan.fmt, colmax_ready=True)
+            return
+        variances = [pf.kernel.variance, pa.kernel.variance]
+        with _Stage(timing, "trsm_stats"):
+            ops.trsm_stats_f16_batch(
+                [b["Tfr_f"], b["Tfr_a"]], [b["Kfr_f"], b["Kfr_a"]], [pf.q_mu, pa.q_mu], pf.num_inducing, N,
+                [bf["Afr"], ba["Afr"]], [bf["stats"], ba["stats"]], variances,
+                As=[bf["A32"], ba["A32"]] if plan.train else None)
+        with _Stage(timing, "expert_cond"):
+            ops.expert_conditional_f16_batch(
+                [bf["Afr"], ba["Afr"]], [b["Lfr_f"], b["Lfr_a"]], [bf["stats"], ba["stats"]], variances,
+                pf.num_inducing, N, self.K, [bf["fmean"], ba["fmean"]], [bf["fvar"], ba["fvar"]],
+                [b["ws_expert"], b["ws_expert2"]],
+                # bounds from _side_work's colnorm_max
+                c_outs=[bf["c_out"], ba["c_out"]] if plan.c_images else None)
+
+    def _chain_f32(self, st, timing, kl_out):
+        """The exact-f32 mode's chain: K1, K4 and K5 per layer on the main stream, then the KL."""
+        for L, layer in self._layers():
+            layer.conditional_kn(st.X, st.LinvT[L], bufs=st.b.layer[L], timing=timing, fmt=st.plan.fmt)
+        if kl_out is not None:
             with _Stage(timing, "gauss_kl"):
                 self.pred_layer.prior_kl(out=kl_out[0:1])
                 self.assign_layer.prior_kl(out=kl_out[1:2])
-        return b["mu_f"], b["var_f"], b["mu_a"], b["var_a"]
 
     def _assign_lik_var(self):
         return None  # SMGPModified: the assignment likelihood's variances
@@ -1018,6 +1022,38 @@ class SMGP(SGP):
         return tuple(t for _, t, _ in self.trainable_parameters())
 
     # ------------------------------------------------------------------ ELBO
+    def _data_term(self, X, Y, train, noise, seed, n_offset, n_total, timing):
+        """What _build_likelihood and elbo_and_grad share up to the data term: the inputs, both
+        layers' conditionals with the KL terms (b["kl"]) and sum_n of the data term
+        (b["data_sum"]).  Returns the step state, the (args, kwargs) that ops.elbo_terms took
+        (ops.elbo_terms_backward takes the same) and (n_batch, num_data)."""
+        X = self.pred_layer.kernel._x(X)
+        N = X.shape[0]
+        Yd = _to_dev(Y, self.device).reshape(-1).contiguous()
+        if Yd.numel() != N:
+            raise ValueError("X and Y must have the same number of rows")
+        st = self._conditionals(X, timing, self._buffers(N, train)["kl"], train)
+        b = st.b
+        mc = self._mc_eps()
+        lik_var = None if mc is not None else self.likelihood.likelihood.variance.reshape(-1)
+        if seed is None and noise is None:
+            seed = self.next_seed()
+        args = (b["mu_f"], b["var_f"], b["mu_a"], b["var_a"], Yd, lik_var, self.num_samples, TAU)
+        kw = dict(noise=noise, seed=seed or 0, n_offset=n_offset, assign_lik_var=self._assign_lik_var(),
+                  multiclass_eps=mc)
+        with _Stage(timing, "elbo_terms"):
+            ops.elbo_terms(*args, out=b["data_sum"], **kw)
+        n_batch = n_total if n_total is not None else N
+        return st, (args, kw), (n_batch, self.num_data if self.num_data is not None else n_batch)
+
+    def _combine(self, b, n_batch, num_data, out64):
+        """The ELBO from the data-term sum and the KL terms: a fresh float32 tensor per call
+        (the reference returns a new value each time), written by the combine kernel itself
+        (no copy launch behind it); out64 receives the float64 value."""
+        e32 = torch.empty((), dtype=torch.float32, device=self.device)
+        ops.elbo_combine(b["data_sum"], b["kl"][0:1], b["kl"][1:2], n_batch, num_data, out=e32, out64=out64)
+        return e32
+
     def _build_likelihood(self, X, Y, noise=None, seed=None, n_offset=0, n_total=None,
                           process_group=None, return64=False, timing=None):
         """ELBO (models.py:69-79) as a 0-d float32 device tensor.
@@ -1026,33 +1062,13 @@ class SMGP(SGP):
         otherwise in-kernel Philox keyed by (seed, global n, s, k).
         n_offset / n_total / process_group: data-parallel sharding over N (each
         rank passes its shard; one all-reduce of the data-term sum)."""
-        X = self.pred_layer.kernel._x(X)
-        N = X.shape[0]
-        Yd = _to_dev(Y, self.device).reshape(-1).contiguous()
-        if Yd.numel() != N:
-            raise ValueError("X and Y must have the same number of rows")
-        b = self._buffers(N)
-        kl = b["kl"]
-        mu_f, var_f, mu_a, var_a = self.conditionals(X, timing=timing, kl_out=kl)
-        mc = self._mc_eps()
-        lik_var = None if mc is not None else self.likelihood.likelihood.variance.reshape(-1)
-        if seed is None and noise is None:
-            seed = self.next_seed()
-        with _Stage(timing, "elbo_terms"):
-            ops.elbo_terms(mu_f, var_f, mu_a, var_a, Yd, lik_var, self.num_samples, TAU,
-                           noise=noise, seed=seed or 0, n_offset=n_offset, out=b["data_sum"],
-                           assign_lik_var=self._assign_lik_var(), multiclass_eps=mc)
+        st, _, (n_batch, num_data) = self._data_term(X, Y, False, noise, seed, n_offset, n_total, timing)
         if process_group is not None:
             import torch.distributed as dist
             with _Stage(timing, "allreduce"):
-                dist.all_reduce(b["data_sum"], op=dist.ReduceOp.SUM, group=process_group)
-        n_batch = n_total if n_total is not None else N
-        num_data = self.num_data if self.num_data is not None else n_batch
-        # a fresh tensor per call (the reference returns a new value each time), written
-        # by the combine kernel itself (no copy launch behind it)
-        e32 = torch.empty((), dtype=torch.float32, device=self.device)
+                dist.all_reduce(st.b["data_sum"], op=dist.ReduceOp.SUM, group=process_group)
         e64 = torch.empty((), dtype=torch.float64, device=self.device)
-        ops.elbo_combine(b["data_sum"], kl[0:1], kl[1:2], n_batch, num_data, out=e32, out64=e64)
+        e32 = self._combine(st.b, n_batch, num_data, e64)
         return e64 if return64 else e32
 
     # ------------------------------------------------------------------ training
@@ -1104,6 +1120,57 @@ class SMGP(SGP):
                 and f.kernel.lengthscales.numel() == a.kernel.lengthscales.numel()
                 and f.Z.stride() == a.Z.stride())
 
+    def _cond_backward(self, st, L, layer, g_mean, g_var, timing):
+        """One layer's conditional backward (x6) from the gradients of its fmean and fvar."""
+        plan, b = st.plan, st.b
+        M = layer.num_inducing
+        with _Stage(timing, "conditional_bwd"):
+            cimg = prep = t_bound = None
+            if plan.c_images:
+                # the forward's C_k images (mgp_conditional_backward_f16c) and, from its side
+                # stream, the q_sqrt-only prep; max |LinvT| from K3's bounded L^-T images
+                cimg = (b["Cfr_" + L], b["colmax_" + L], ops.image_bound(b["Lfr_" + L], M, K=layer.num_latent_gps))
+                prep = b["cprep_" + L]
+                if plan.bounded:
+                    t_bound = ops.image_bound(b["Tfr_" + L], M, K=1)
+            return ops.conditional_backward_x6(b["Afr_" + L], b["A32_" + L], layer.q_sqrt, layer.q_mu,
+                                               st.LinvT[L], g_mean, g_var, M, st.X.shape[0],
+                                               workspace=b["ws_cbwd"], fmt=plan.fmt, c_images=cimg, prep=prep,
+                                               t_bound=t_bound)
+
+    def _tail_backward(self, st, L, name, layer, g, timing):
+        """One layer's Cholesky and kernel backward (Kuf and Kuu): its gradient blocks."""
+        with _Stage(timing, "chol_bwd"):
+            gKuu = ops.chol_backward(st.L[L], st.LinvT[L], g["g_Lm"])
+        with _Stage(timing, "rbf_bwd"):
+            k = layer.kernel
+            gZ, gvar, gls = k.backward(st.X, layer.Z, g["g_Kuf"], accumulate=True, g_var=g["g_var"],
+                                       gZ=torch.zeros_like(layer.Z),
+                                       g_ls=torch.zeros(k.lengthscales.numel(), dtype=torch.float64,
+                                                        device=self.device))
+            k.backward(layer.Z, layer.Z, gKuu, symmetric=True, accumulate=True, gZ=gZ, g_var=gvar, g_ls=gls)
+        return {name + ".Z": gZ, name + ".variance": gvar, name + ".lengthscales": gls,
+                name + ".q_mu": g["g_q_mu"], name + ".q_sqrt": g["g_q_sqrt"]}
+
+    def _tail_backward_pair(self, st, order, gs, timing):
+        """_tail_backward of both layers with one Cholesky and one RBF backward launch."""
+        with _Stage(timing, "chol_bwd"):
+            gKuus = ops.chol_backward_batch([st.L[L] for L, *_ in order], [st.LinvT[L] for L, *_ in order],
+                                            [g["g_Lm"] for g in gs])
+        with _Stage(timing, "rbf_bwd"):
+            layers = [layer for _, _, layer, _ in order]
+            # gZ / g_ls written by the finish (accumulate 2: no zero fills), g_var added
+            # to the conditional backward's part
+            gZs = [torch.empty(layer.Z.shape, dtype=layer.Z.dtype, device=self.device) for layer in layers]
+            glss = [torch.empty(layer.kernel.lengthscales.numel(), dtype=torch.float64, device=self.device)
+                    for layer in layers]
+            ops.rbf_backward_batch(st.X, [layer.Z for layer in layers], [layer.kernel.variance for layer in layers],
+                                   [layer.kernel.lengthscales for layer in layers], [g["g_Kuf"] for g in gs],
+                                   gKuus, gZs, [g["g_var"] for g in gs], glss, accumulate=2)
+        return [{name + ".Z": gZ, name + ".variance": g["g_var"], name + ".lengthscales": gls,
+                 name + ".q_mu": g["g_q_mu"], name + ".q_sqrt": g["g_q_sqrt"]}
+                for (_, name, _, _), g, gZ, gls in zip(order, gs, gZs, glss)]
+
     def elbo_and_grad(self, X, Y, noise=None, seed=None, n_offset=0, n_total=None, process_group=None,
                       timing=None, unconstrained=False):
         """ELBO (0-d float32) and its gradient w.r.t. every constrained parameter of
@@ -1114,115 +1181,43 @@ class SMGP(SGP):
         K6 backward -> per layer conditional backward (x6) -> Cholesky backward -> RBF
         backward (Kuf and Kuu) -> + KL.  Data-parallel: one all-reduce of the
         data-term gradients per step (the KL part is added after it)."""
-        X = self.pred_layer.kernel._x(X)
-        N = X.shape[0]
-        Yd = _to_dev(Y, self.device).reshape(-1).contiguous()
-        b = self._buffers(N, train=True)
-        kl = b["kl"]
-        mu_f, var_f, mu_a, var_a = self.conditionals(X, timing=timing, kl_out=kl, train=True)
-        mc = self._mc_eps()
-        lik_var = None if mc is not None else self.likelihood.likelihood.variance.reshape(-1)
-        alv = self._assign_lik_var()
-        if seed is None and noise is None:
-            seed = self.next_seed()
-        with _Stage(timing, "elbo_terms"):
-            ops.elbo_terms(mu_f, var_f, mu_a, var_a, Yd, lik_var, self.num_samples, TAU, noise=noise,
-                           seed=seed or 0, n_offset=n_offset, out=b["data_sum"], assign_lik_var=alv,
-                           multiclass_eps=mc)
-        n_batch = n_total if n_total is not None else N
+        st, (args, kw), (n_batch, num_data) = self._data_term(X, Y, True, noise, seed, n_offset, n_total, timing)
+        b = st.b
         with _Stage(timing, "elbo_terms_bwd"):
-            G, glv, glva = ops.elbo_terms_backward(mu_f, var_f, mu_a, var_a, Yd, lik_var, self.num_samples, TAU,
-                                                   noise=noise, seed=seed or 0, n_offset=n_offset,
-                                                   scale=1.0 / n_batch, assign_lik_var=alv, G=b["G"],
-                                                   multiclass_eps=mc)
-        grads = {"lik_variance": glv} if mc is None else {}
-        if alv is not None:
+            G, glv, glva = ops.elbo_terms_backward(*args, scale=1.0 / n_batch, G=b["G"], **kw)
+        grads = {"lik_variance": glv} if kw["multiclass_eps"] is None else {}
+        if kw["assign_lik_var"] is not None:
             grads["assign_lik_variance"] = glva
-
-        def cond_backward(L, layer, gi, ws):
-            M = layer.num_inducing
-            with _Stage(timing, "conditional_bwd"):
-                cimg = None
-                if "Cfr_" + L in b:  # the forward's C_k images (mgp_conditional_backward_f16c)
-                    cimg = (b["Cfr_" + L], b["colmax_" + L],
-                            ops.image_bound(b["Lfr_" + L], M, K=layer.num_latent_gps))
-                prep = b["cprep_" + L] if cimg is not None and b.get("cprep_done") else None
-                tb = ops.image_bound(b["Tfr_" + L], M, K=1) if prep is not None and b.get("lt_bounded") and _T_BOUND else None
-                return ops.conditional_backward_x6(b["Afr_" + L], b["A32_" + L], layer.q_sqrt,
-                                                   layer.q_mu, b["LinvT_" + L], G[gi], G[gi + 1], M, N,
-                                                   workspace=ws, fmt=forward_image_format(True),
-                                                   c_images=cimg, prep=prep, t_bound=tb)
-
-        def tail_backward(L, name, layer, g):
-            with _Stage(timing, "chol_bwd"):
-                gKuu = ops.chol_backward(b["L_" + L], b["LinvT_" + L], g["g_Lm"])
-            with _Stage(timing, "rbf_bwd"):
-                k = layer.kernel
-                gZ, gvar, gls = k.backward(X, layer.Z, g["g_Kuf"], accumulate=True, g_var=g["g_var"],
-                                           gZ=torch.zeros_like(layer.Z),
-                                           g_ls=torch.zeros(k.lengthscales.numel(), dtype=torch.float64,
-                                                            device=self.device))
-                k.backward(layer.Z, layer.Z, gKuu, symmetric=True, accumulate=True, gZ=gZ, g_var=gvar, g_ls=gls)
-            return {name + ".Z": gZ, name + ".variance": gvar, name + ".lengthscales": gls,
-                    name + ".q_mu": g["g_q_mu"], name + ".q_sqrt": g["g_q_sqrt"]}
-
-        def tail_backward_batch(order, gs):
-            with _Stage(timing, "chol_bwd"):
-                gKuus = ops.chol_backward_batch([b["L_" + L] for L, *_ in order], [b["LinvT_" + L] for L, *_ in order],
-                                                [g["g_Lm"] for g in gs])
-            with _Stage(timing, "rbf_bwd"):
-                layers = [layer for _, _, layer, _ in order]
-                # gZ / g_ls written by the finish (accumulate 2: no zero fills), g_var added
-                # to the conditional backward's part
-                alloc = torch.empty if _RBF_NO_FILL else torch.zeros
-                gZs = [alloc(layer.Z.shape, dtype=layer.Z.dtype, device=self.device) for layer in layers]
-                glss = [alloc(layer.kernel.lengthscales.numel(), dtype=torch.float64, device=self.device)
-                        for layer in layers]
-                ops.rbf_backward_batch(X, [layer.Z for layer in layers], [layer.kernel.variance for layer in layers],
-                                       [layer.kernel.lengthscales for layer in layers], [g["g_Kuf"] for g in gs],
-                                       gKuus, gZs, [g["g_var"] for g in gs], glss,
-                                       accumulate=2 if _RBF_NO_FILL else 1)
-            return [{name + ".Z": gZ, name + ".variance": g["g_var"], name + ".lengthscales": gls,
-                     name + ".q_mu": g["g_q_mu"], name + ".q_sqrt": g["g_q_sqrt"]}
-                    for (_, name, _, _), g, gZ, gls in zip(order, gs, gZs, glss)]
-
+        head = [b["data_sum"]] + list(grads.values())   # reduced with the first layer's bucket
         pending = []
-
-        def reduce_bucket(layer_grads):
-            if process_group is not None:
-                # one bucket per layer (the first also carries the data-term sum and the
-                # likelihood gradients); the pred layer's is in flight while the assign
-                # layer's backward still runs
-                from .distributed import allreduce_gradients_async
-                bucket = list(layer_grads.values())
-                if not pending:
-                    bucket = [b["data_sum"]] + list(grads.values()) + bucket
-                pending.append(allreduce_gradients_async(bucket, group=process_group))
-
         # the two layers in order on this stream (a side stream for one layer's Cholesky /
         # RBF backward beside the other's conditional backward measured slower: the
         # matrix-core kernel starves the small ones, DESIGN.md round-4 results); with
         # matching shapes both layers' Cholesky and RBF backward run as one batch each
         order = (("f", "pred", self.pred_layer, 0), ("a", "assign", self.assign_layer, 2))
-        if _TAIL_BATCH and self._tail_batchable():
-            gs = [cond_backward(L, layer, gi, b["ws_cbwd"]) for L, _, layer, gi in order]
-            for layer_grads in tail_backward_batch(order, gs):
-                reduce_bucket(layer_grads)
-                grads.update(layer_grads)
+        if st.plan.tail_paired:
+            gs = [self._cond_backward(st, L, layer, G[gi], G[gi + 1], timing) for L, _, layer, gi in order]
+            layer_grads = self._tail_backward_pair(st, order, gs, timing)
         else:
-            for L, name, layer, gi in order:
-                layer_grads = tail_backward(L, name, layer, cond_backward(L, layer, gi, b["ws_cbwd"]))
-                reduce_bucket(layer_grads)
-                grads.update(layer_grads)
+            layer_grads = (self._tail_backward(st, L, name, layer,
+                                               self._cond_backward(st, L, layer, G[gi], G[gi + 1], timing), timing)
+                           for L, name, layer, gi in order)
+        for lg in layer_grads:   # (unpaired: computed here, layer by layer)
+            if process_group is not None:
+                # one bucket per layer (the first also carries the data-term sum and the
+                # likelihood gradients); the pred layer's is in flight while the assign
+                # layer's backward still runs
+                from .distributed import allreduce_gradients_async
+                bucket = list(lg.values())
+                pending.append(allreduce_gradients_async(bucket if pending else head + bucket, group=process_group))
+            grads.update(lg)
         if process_group is not None:
             with _Stage(timing, "allreduce"):
                 for pb in pending:
                     pb.wait()
-        num_data = self.num_data if self.num_data is not None else n_batch
         for name, layer in (("pred", self.pred_layer), ("assign", self.assign_layer)):
             ops.kl_grad(layer.q_mu, layer.q_sqrt, num_data, grads[name + ".q_mu"], grads[name + ".q_sqrt"])
-        e32 = torch.empty((), dtype=torch.float32, device=self.device)   # fresh per call, no copy launch
-        ops.elbo_combine(b["data_sum"], kl[0:1], kl[1:2], n_batch, num_data, out=e32, out64=b["elbo64"])
+        e32 = self._combine(b, n_batch, num_data, b["elbo64"])
         if unconstrained:   # d/du = d/dtheta * softplus'(u) = d/dtheta * (1 - exp(-theta)) for positive ones
             for name, t, kind in self.trainable_parameters():
                 if kind == "positive":

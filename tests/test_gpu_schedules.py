@@ -1,9 +1,9 @@
 """Every step schedule (config.STEP_SCHEDULES) computes the same bits.
 
 The schedules only move the Cholesky-independent work of a step (K1, the tril(q_sqrt)
-images, the KL) between the main and the side stream, and the k1a_* ones run the
-layers' K4 / K5 per layer instead of in one launch each (the batch entries are
-bit-identical to the per-layer ones).  So, for a fixed Philox key, the ELBO of
+images, the KL) between K3's step launches, the side stream and the main stream ("serial":
+everything on the main stream, so a cross-stream race shows as a difference from it).
+So, for a fixed Philox key, the ELBO of
 _build_likelihood (models.py:69-79) and the ELBO and every gradient block of
 elbo_and_grad (utils/training_utils.py:10) must be bit-identical to the default
 schedule's.  Shapes: one problem with equal M for both layers (the batched K3 / K4 /

@@ -85,6 +85,8 @@ def test_config_step_schedule_knob():
             assert config.step_schedule() == v
         with pytest.raises(ValueError):
             config.set_step_schedule("k1_first")
+        with pytest.raises(ValueError):   # removed with its measured-slower siblings
+            config.set_step_schedule("k1_main")
     finally:
         config.set_step_schedule(old)
 

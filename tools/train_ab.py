@@ -16,24 +16,9 @@ def main():
     rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 3
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 30
     label = sys.argv[3] if len(sys.argv) > 3 else os.environ.get("MGP_HIP_LIB", "in-tree")
-    if "colmaxmain" in sys.argv[4:]:   # colnorm_max on the main stream before K5 (before round 4's move)
-        from modulatedgps_amd import models
-        models._COLMAX_SIDE = False
     if "k4single" in sys.argv[4:]:   # one K4 launch per layer (the round-4 default before the batch)
         from modulatedgps_amd import models
         models._K4_BATCHED = False
-    if "tailper" in sys.argv[4:]:   # Cholesky / RBF backward per layer (before round 5's batch)
-        from modulatedgps_amd import models
-        models._TAIL_BATCH = False
-    if "fill" in sys.argv[4:]:   # zero-filled gZ / g_ls + accumulate (before the overwrite mode)
-        from modulatedgps_amd import models
-        models._RBF_NO_FILL = False
-    if "noprep" in sys.argv[4:]:   # the C-images backward's q_sqrt launches inside it (before the prep)
-        from modulatedgps_amd import models
-        models._COND_PREP = False
-    if "notb" in sys.argv[4:]:   # max |LinvT| reduced inside the backward (before the K3 bound hand-over)
-        from modulatedgps_amd import models
-        models._T_BOUND = False
     if "adamper" in sys.argv[4:]:   # one Adam launch per parameter block (before round 5's set)
         from modulatedgps_amd import training
         training._ADAM_SET = False
